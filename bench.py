@@ -5,10 +5,15 @@ A "step" is one batch of N timestamped requests, resident in HBM, pushed through
 whole hot path (partition -> per-region sequential semantics -> results in caller
 order). Steps are consecutive slices of one synthetic trace, so state carries over
 and time moves forward exactly as in a replay.
+A run of more steps than fit in HBM at once (resident_steps) generates and times them chunk
+by chunk; generation is never timed.
 
 Default workload (N=1): BASELINE.json configs[2], the largest single-GPU configuration —
 sliding window 1000/min (SlidingWindowRateLimiter.java:158-180), 100M keys Zipf s=1.1,
-256M-request batches spanning 60 s each. The same JSON line carries configs[1] (token
+256M-request batches spanning 60 s each. A plain run sets up, warms up, times the steps and
+prints the headline line; `--dump-outputs DIR` also writes what the last timed step returned.
+With `--full` the line also carries the CPU baseline and batch-0 parity of that config and,
+on one GPU, configs[1] (token
 bucket cap 50 at 10/s, 1M keys uniform, 64M-request batches; `tb_uniform`), the per-GPU
 share of configs[4] (TB 50@10/s + SW 1000/min, Zipf s=1.1, 125M keys, 2^27 requests per
 step; `zipf_1b`), the per-GPU share of configs[3] (10 limiters, 125M keys, 2^27 requests per
@@ -146,7 +151,7 @@ def hbm_footprint(name, n, ws, steps, warm, router="capi", recv_cap=0, table_sca
     cfg = CONFIGS[name]
     n_lim = len(cfg["limiters"])
     req_in = 8 + 8 + 4 + (2 if n_lim > 1 else 0)
-    out = {"inputs": (steps + warm) * n * req_in,
+    out = {"inputs": min(steps + warm, resident_steps(n, n_lim)) * n * req_in,
            "outputs": n * (1 + 8) + (n * 8 if parity_tokens else 0)}
     cap = engine_max_batch(n, ws, router)
     rcap = min(recv_cap or cap, cap) if ws > 1 else n
@@ -326,11 +331,21 @@ def parity_text(dec_ok, bal, n):
     return s
 
 
-def make_inputs(eng, cfg, n, ws, rank, total_steps, dev):
+RESIDENT_INPUT_BYTES = 144e9    # inputs a rank keeps in HBM at a time (half of the 288 GB)
+
+
+def resident_steps(n, n_lim):
+    """Steps whose inputs are resident at once: a run of more steps generates and times them
+    in chunks of this many (the driver's 20 + 5 steps of 256M requests are one chunk)."""
+    return max(1, int(RESIDENT_INPUT_BYTES // (n * (REQ_IN + (2 if n_lim > 1 else 0)))))
+
+
+def make_inputs(eng, cfg, n, ws, rank, total_steps, dev, first=0, count=None):
+    """Steps first .. first + count - 1 (default: all) of the total_steps-step trace."""
     n_global_total = total_steps * ws * n
     n_lim = len(cfg["limiters"])
     inputs = []
-    for s in range(total_steps):
+    for s in range(first, total_steps if count is None else first + count):
         keys = torch.empty(n, dtype=torch.int64, device=dev)
         permits = torch.empty(n, dtype=torch.int32, device=dev)
         now = torch.empty(n, dtype=torch.int64, device=dev)
@@ -355,9 +370,32 @@ def plan_directory(router, cfg, inputs, n, k=4096, sample=1 << 22):
     return router.plan_directory(kk, cc, int(keys.numel()), k)
 
 
-def run(name, args, ws, rank, local, dev, rehearse, steps, warm, parity_tokens):
+DUMP_SAMPLE = 1 << 21          # requests of the last step that --dump-outputs keeps
+DUMP_SEED = 0x5EED0D07
+
+
+def dump_outputs(path, rank, n, allowed, remaining):
+    """--dump-outputs: what the last timed step handed its caller, as <name>.npy. A step
+    returns `allowed` (u8) and `remaining` (i64) per request in caller order; a batch larger
+    than DUMP_SAMPLE is cut to a fixed seeded sample of its request indices (`index.npy`,
+    ascending), 40 MB in all. Ranks above 0 add `_rank<r>` to the names."""
+    os.makedirs(path, exist_ok=True)
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE, dtype=np.int64))
+    else:
+        idx = np.arange(n, dtype=np.int64)
+    sel = torch.from_numpy(idx).to(allowed.device)
+    sfx = f"_rank{rank}" if rank else ""
+    np.save(os.path.join(path, f"index{sfx}.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, f"allowed{sfx}.npy"), allowed[:n][sel].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, f"remaining{sfx}.npy"),
+            remaining[:n][sel].cpu().numpy().astype(np.float64))
+
+
+def run(name, args, ws, rank, local, dev, rehearse, steps, warm, parity_tokens, keep=True,
+        dump_dir=None):
     """Time `steps` steps of config `name` after `warm` warmup steps; returns the line's
-    dict and what the CPU baseline needs (batch 0's inputs and GPU results)."""
+    dict and what the CPU baseline needs (batch 0's inputs and, if `keep`, GPU results)."""
     cfg = CONFIGS[name]
     n = (args.batch if name == args.config else 0) or cfg["batch"]
     total_steps = steps + warm
@@ -381,7 +419,11 @@ def run(name, args, ws, rank, local, dev, rehearse, steps, warm, parity_tokens):
         k, v = kv.split("=")
         eng.tune(k, int(v))
     n_lim = len(cfg["limiters"])
-    inputs = make_inputs(eng, cfg, n, ws, rank, total_steps, dev)
+    # the steps' inputs, resident in HBM chunk by chunk (one chunk unless the run is long)
+    chunk = resident_steps(n, n_lim)
+    base = 0
+    inputs = make_inputs(eng, cfg, n, ws, rank, total_steps, dev, 0, min(chunk, total_steps))
+    in0 = inputs[0] if keep and inputs else None       # batch 0, for the CPU baseline
     allowed = torch.empty(n, dtype=torch.uint8, device=dev)
     remaining = torch.empty(n, dtype=torch.int64, device=dev)
     has_tb = any(x[0] == rl_amd.TB for x in cfg["limiters"])
@@ -398,7 +440,7 @@ def run(name, args, ws, rank, local, dev, rehearse, steps, warm, parity_tokens):
                             exchange_device="cpu" if rehearse else None)
 
             def step(s, tok=None):
-                k, p, t, li = inputs[s]
+                k, p, t, li = inputs[s - base]
                 router.step(k, p, t, allowed, remaining, li)
         else:
             from rl_amd.capi_router import CRouter
@@ -408,11 +450,11 @@ def run(name, args, ws, rank, local, dev, rehearse, steps, warm, parity_tokens):
                 directory = plan_directory(router, cfg, inputs, n)
 
             def step(s, tok=None):
-                k, p, t, li = inputs[s]
+                k, p, t, li = inputs[s - base]
                 router.step(n, k, p, t, li, allowed, remaining)
     else:
         def step(s, tok=None):
-            k, p, t, li = inputs[s]
+            k, p, t, li = inputs[s - base]
             eng.execute_device(n, k, p, t, li, None, allowed, remaining, tok)
 
     # Warmup steps. Step 0 also returns the TB balances (parity); steps 1.. of the warmup
@@ -420,32 +462,45 @@ def run(name, args, ws, rank, local, dev, rehearse, steps, warm, parity_tokens):
     # run without them.
     keep0 = None
     stages = {}
-    for s in range(warm):
-        if s == 1:
-            eng.tune("stage_timing", 1)
-        step(s, tokens0 if s == 0 else None)
-        if s == 0:
+    warm_stats = None
+    elapsed = 0.0
+    while base < total_steps:
+        if base:
+            inputs = None              # the previous chunk's buffers go back to the allocator
+            inputs = make_inputs(eng, cfg, n, ws, rank, total_steps, dev, base,
+                                 min(chunk, total_steps - base))
             eng.sync()
             torch.cuda.synchronize()
-            keep0 = (allowed.cpu().numpy(), remaining.cpu().numpy(),
-                     None if tokens0 is None else tokens0.cpu().numpy())
-    if warm > 1:
-        stages = eng.stage_times()
-    warm_stats = eng.stats()          # the batch whose stage times were just read (routed count)
-    eng.tune("stage_timing", 1 if args.stage_timing else 0)
-    del tokens0
-
-    if ws > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for s in range(warm, total_steps):
-        step(s)
-    eng.sync()
-    torch.cuda.synchronize()
-    if ws > 1:
-        dist.barrier()
-    elapsed = time.perf_counter() - t0
+        end = base + len(inputs)
+        for s in range(base, min(warm, end)):
+            if s == 1:
+                eng.tune("stage_timing", 1)
+            step(s, tokens0 if s == 0 else None)
+            if s == 0 and keep:
+                eng.sync()
+                torch.cuda.synchronize()
+                keep0 = (allowed.cpu().numpy(), remaining.cpu().numpy(),
+                         None if tokens0 is None else tokens0.cpu().numpy())
+        if end > warm:
+            if warm_stats is None:
+                if warm > 1:
+                    stages = eng.stage_times()
+                warm_stats = eng.stats()  # the batch whose stage times were just read (routed count)
+                eng.tune("stage_timing", 1 if args.stage_timing else 0)
+                tokens0 = None
+            # this chunk's timed steps: one uninterrupted loop, barrier + sync on both sides
+            if ws > 1:
+                dist.barrier()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for s in range(max(base, warm), end):
+                step(s)
+            eng.sync()
+            torch.cuda.synchronize()
+            if ws > 1:
+                dist.barrier()
+            elapsed += time.perf_counter() - t0
+        base = end
     if ws > 1:
         router.finish()                    # collective: raises on every rank on an engine error
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearse else dev)
@@ -456,6 +511,8 @@ def run(name, args, ws, rank, local, dev, rehearse, steps, warm, parity_tokens):
     used = free0 - torch.cuda.mem_get_info(dev)[0]     # this rank's device bytes at the end
     if args.stage_timing:
         stages = eng.stage_times()
+    if dump_dir:
+        dump_outputs(dump_dir, rank, n, allowed, remaining)
     ms_per_step = elapsed / steps * 1e3
     value = ws * n * steps / elapsed
 
@@ -534,7 +591,7 @@ def run(name, args, ws, rank, local, dev, rehearse, steps, warm, parity_tokens):
     if router is not None and hasattr(router, "close"):
         router.close()
     eng.close()
-    return out, inputs[0], keep0
+    return out, in0, keep0
 
 
 def main():
@@ -544,9 +601,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="sw_zipf", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=0, help="requests per GPU per step (override)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the CPU baseline and check batch-0 parity against it and, at N=1, "
+                         "add the tb_uniform / zipf_1b / mixed_tenants / config1 keys to the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (a fixed sample of a large batch) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the CPU baseline and everything that needs it")
     ap.add_argument("--no-extra", action="store_true",
-                    help="N=1: skip the extra tb_uniform / zipf_1b / mixed_tenants / config1 keys of the line")
+                    help="--full, N=1: skip the extra tb_uniform / zipf_1b / mixed_tenants / config1 keys of the line")
     ap.add_argument("--cpu-sample", type=int, default=1 << 26)
     ap.add_argument("--tune", action="append", default=[],
                     help="engine knob key=value (rl_tune), e.g. hot_threshold=32768")
@@ -584,9 +648,10 @@ def main():
     # that slice is the head of the whole trace: the oracle's sequential replay of it alone is
     # exact at any world size. At N>1 the router returns no token balances (decisions and
     # remaining are compared).
-    baseline = rank == 0 and not args.no_cpu_baseline
+    baseline = rank == 0 and args.full and not args.no_cpu_baseline
     out, in0, keep0 = run(args.config, args, ws, rank, local, dev, rehearse, args.steps,
-                          args.warmup, parity_tokens=baseline and ws == 1)
+                          args.warmup, parity_tokens=baseline and ws == 1, keep=baseline,
+                          dump_dir=args.dump_outputs)
     if baseline:
         k0, p0, t0_, l0 = in0
         cb, dec_ok, bal, m = cpu_baseline(CONFIGS[args.config], k0, p0, t0_, l0, args.cpu_sample,

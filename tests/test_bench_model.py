@@ -25,6 +25,19 @@ def test_footprint_fits_288gb(name, ws):
     assert fp["fits_288GB"]
 
 
+@pytest.mark.parametrize("name", sorted(bench.CONFIGS))
+def test_long_run_inputs_stay_bounded(name):
+    """Any --steps fits: inputs are resident a chunk at a time, the driver's 25 steps in one."""
+    cfg = bench.CONFIGS[name]
+    n, n_lim = cfg["batch"], len(cfg["limiters"])
+    c = bench.resident_steps(n, n_lim)
+    assert c >= DRIVER["steps"] + DRIVER["warm"]
+    assert bench.resident_steps(1 << 40, 1) == 1
+    fp = bench.hbm_footprint(name, n, 1, 100_000, 5, parity_tokens=True)
+    assert fp["inputs"] == c * n * (20 + (2 if n_lim > 1 else 0)) <= bench.RESIDENT_INPUT_BYTES
+    assert fp["total"] + fp["tables"] + 4e9 + fp["inputs"] // c <= bench.HBM_BYTES_PER_GPU
+
+
 def test_footprint_sw_zipf_gpus8_components():
     """The verdict's case: --gpus 8 --config sw_zipf --steps 20 --warmup 5."""
     n = 1 << 28
@@ -49,6 +62,32 @@ def test_traffic_keyed_by_workload(tmp_path, monkeypatch):
         assert v > 0 and src == d["_meta"][name] and os.path.isdir(os.path.join(bench.ROOT, src))
         assert bench.load_pmc(name, "step", bench.CONFIGS[name]["batch"], 2) == (None, None)
         assert bench.load_pmc(name, "step", 1 << 21, 1) == (None, None)
+
+
+@pytest.mark.parametrize("n", [1000, bench.DUMP_SAMPLE, bench.DUMP_SAMPLE + 7, 5 << 20])
+def test_dump_outputs_whole_or_fixed_sample(tmp_path, n):
+    """--dump-outputs: float .npy of the step's results, whole up to DUMP_SAMPLE requests and
+    at the same seeded ascending request indices above it; buffers longer than n are cut."""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(n)
+    a = rng.integers(0, 2, n + 3, dtype=np.uint8)
+    r = rng.integers(-3, 1000, n + 3, dtype=np.int64)
+    for sub, rank in (("x", 0), ("y", 0), ("y", 1)):
+        bench.dump_outputs(str(tmp_path / sub), rank, n, torch.from_numpy(a), torch.from_numpy(r))
+    idx, da, dr = (np.load(tmp_path / "x" / f"{k}.npy") for k in ("index", "allowed", "remaining"))
+    assert (idx.dtype, da.dtype, dr.dtype) == (np.float64, np.float32, np.float64)
+    m = min(n, bench.DUMP_SAMPLE)
+    assert idx.shape == da.shape == dr.shape == (m,)
+    i = idx.astype(np.int64)
+    assert i[0] >= 0 and i[-1] < n and np.all(np.diff(i) >= 0)
+    if m == n:
+        assert np.array_equal(i, np.arange(n))
+    assert np.array_equal(da, a[i]) and np.array_equal(dr, r[i])
+    for k in ("index", "allowed", "remaining"):          # same arguments, same files; ranks apart
+        assert np.array_equal(np.load(tmp_path / "y" / f"{k}.npy"), np.load(tmp_path / "x" / f"{k}.npy"))
+        assert np.array_equal(np.load(tmp_path / "y" / f"{k}_rank1.npy"), np.load(tmp_path / "x" / f"{k}.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "x").iterdir()) <= 64 << 20
 
 
 def test_walk_tables_only_where_a_key_can_walk():
