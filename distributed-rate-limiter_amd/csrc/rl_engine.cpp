@@ -190,6 +190,7 @@ struct rl_engine {
     bool auto_grow = true;                  // !RL_OPT_FIXED_CAPACITY
     uint32_t inject_fail = 0;               // rl_tune("fail_batches"): tests of callers' error paths
     uint64_t grows = 0;                     // region-count doublings done (rl_batch_stats)
+    unsigned long long* retry_dbg = nullptr; // measurement builds (RL_RETRY_COUNT): k_retry_after's counters
 };
 
 #define HIP_OK(x)                                                      \
@@ -352,7 +353,7 @@ extern "C" void rl_destroy(rl_engine* e) {
     dfree(e->walk_tab);
     dfree(e->route_list); dfree(e->route_start); dfree(e->route_cnt);
     dfree(e->order); dfree(e->order_meta); dfree(e->solo_list);
-    dfree(e->d_stats);
+    dfree(e->d_stats); dfree(e->retry_dbg);
     dfree(e->s_key); dfree(e->s_permits); dfree(e->s_now); dfree(e->s_lim); dfree(e->s_op);
     dfree(e->s_allowed); dfree(e->s_remaining); dfree(e->s_tokens);
     dfree(e->route_scratch); dfree(e->route_counts); dfree(e->d_dir);
@@ -1131,6 +1132,88 @@ extern "C" int rl_reset(rl_engine* e, uint16_t limiter, size_t n, const uint64_t
     return admin_op(e, limiter, n, key_hash, now_ns, RL_OP_RESET, nullptr);
 }
 
+// ---------------------------------------------------------------- retry-after queries
+// One launch of k_retry_after on the engine stream: behind every batch submitted before it
+// (the decision stage, the hot chains' side stream and the unpermute all run on or are joined
+// on e->stream, with RL_OPT_PIPELINE too: only a batch's partition runs elsewhere). It reads
+// the limiter table as uploaded by the last growth and touches no batch scratch, statistic or
+// status word.
+static int run_retry_device(rl_engine* e, size_t n, const uint64_t* key, const int32_t* permits,
+                            const int64_t* now_ns, const uint16_t* limiter, const uint8_t* skip,
+                            int64_t* wait_ms) {
+    RetryArgs ra{};
+    ra.key = key; ra.permits = permits; ra.now_ns = now_ns; ra.limiter = limiter; ra.skip = skip;
+    ra.wait_ms = wait_ms;
+    ra.lims = e->d_lims; ra.n = (uint32_t)n; ra.n_lim = (uint32_t)e->lims.size();
+    ra.shard_bits = e->shard_bits;
+#ifdef RL_RETRY_COUNT
+    if (!e->retry_dbg) {
+        if (dalloc(&e->retry_dbg, 3) != RL_OK) return RL_E_NOMEM;
+        HIP_OK(hipMemset(e->retry_dbg, 0, 3 * sizeof(unsigned long long)));
+    }
+    ra.dbg = e->retry_dbg;
+#endif
+    HIP_OK(launch_retry_after(ra, e->stream));
+    return RL_OK;
+}
+
+extern "C" int rl_retry_after_device(rl_engine* e, size_t n, const uint64_t* key_hash,
+                                     const int32_t* permits, const int64_t* now_ns,
+                                     const uint16_t* limiter, const uint8_t* skip,
+                                     int64_t* wait_ms, void* stream) {
+    if (!e) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (n > e->opts.max_batch) return RL_E_TOO_LARGE;
+    if (n == 0) return RL_OK;
+    if (!key_hash || !permits || !now_ns || !wait_ms) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    hipStream_t user = (hipStream_t)stream;
+    if (user && user != e->stream) {
+        // order the engine stream after the caller's work, and the caller's after ours
+        hipEvent_t ev;
+        HIP_OK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        HIP_OK(hipEventRecord(ev, user));
+        HIP_OK(hipStreamWaitEvent(e->stream, ev, 0));
+        int rc = run_retry_device(e, n, key_hash, permits, now_ns, limiter, skip, wait_ms);
+        HIP_OK(hipEventRecord(ev, e->stream));
+        HIP_OK(hipStreamWaitEvent(user, ev, 0));
+        (void)hipEventDestroy(ev);
+        return rc;
+    }
+    return run_retry_device(e, n, key_hash, permits, now_ns, limiter, skip, wait_ms);
+}
+
+extern "C" int rl_retry_after(rl_engine* e, size_t n, const uint64_t* key_hash, const int32_t* permits,
+                              const int64_t* now_ns, const uint16_t* limiter, const uint8_t* skip,
+                              int64_t* wait_ms) {
+    if (!e) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (n > e->opts.max_batch) return RL_E_TOO_LARGE;
+    if (n == 0) return RL_OK;
+    if (!key_hash || !permits || !now_ns || !wait_ms) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    // as the host-buffer batch calls: the last batch's status is collected first, which applies
+    // the table growth it asked for (rl_last_status returns that same status afterwards)
+    const int st = collect_status(e);
+    if (st == RL_E_DEVICE) return st;
+    int rc = ensure_staging(e, n);
+    if (rc != RL_OK) return rc;
+    hipStream_t s = e->stream;
+    HIP_OK(hipMemcpyAsync(e->s_key, key_hash, n * 8, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(e->s_permits, permits, n * 4, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(e->s_now, now_ns, n * 8, hipMemcpyHostToDevice, s));
+    if (limiter) HIP_OK(hipMemcpyAsync(e->s_lim, limiter, n * 2, hipMemcpyHostToDevice, s));
+    if (skip) HIP_OK(hipMemcpyAsync(e->s_op, skip, n, hipMemcpyHostToDevice, s));
+    rc = run_retry_device(e, n, e->s_key, e->s_permits, e->s_now, limiter ? e->s_lim : nullptr,
+                          skip ? e->s_op : nullptr, e->s_remaining);
+    if (rc != RL_OK) { (void)hipStreamSynchronize(s); return rc; }
+    HIP_OK(hipMemcpyAsync(wait_ms, e->s_remaining, n * 8, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    for (size_t i = 0; i < n; ++i)
+        if (wait_ms[i] == RL_RETRY_INVALID) return RL_E_INVALID_REQUEST;
+    return RL_OK;
+}
+
 extern "C" int rl_batch_stats_get(rl_engine* e, rl_batch_stats* out) {
     if (!e || !out) return RL_E_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
@@ -1577,6 +1660,15 @@ extern "C" int rl_debug_fetch(rl_engine* e, const char* what, void* out, size_t 
         HIP_OK(hipMemcpy(out, B.bin_total, nb, hipMemcpyDeviceToHost));
         return (int)(nb / sizeof(uint32_t));
     }
+#ifdef RL_RETRY_COUNT
+    if (std::strcmp(what, "retry_counts") == 0) {    // {searches, bisections, buckets probed}
+        if (!e->retry_dbg || bytes < 3 * sizeof(unsigned long long)) return RL_E_INVALID_ARG;   // since the last fetch
+        HIP_OK(hipStreamSynchronize(e->stream));
+        HIP_OK(hipMemcpy(out, e->retry_dbg, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        HIP_OK(hipMemset(e->retry_dbg, 0, 3 * sizeof(unsigned long long)));
+        return 3;
+    }
+#endif
     return RL_E_INVALID_ARG;
 }
 

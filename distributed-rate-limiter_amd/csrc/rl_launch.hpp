@@ -412,6 +412,24 @@ hipError_t launch_unpermute(const UnpermArgs& a, int res_bytes, hipStream_t s);
 hipError_t launch_fill_invalid(uint8_t* allowed, int64_t* remaining, double* tok, uint32_t n,
                                hipStream_t s);
 hipError_t launch_synth(const SynthArgs& a, hipStream_t s);
+// Retry-after queries (rl_retry.hip): a read-only gather over the state tables, one answer per
+// query (wait_ms >= 0, kRetryNever, kRetryInvalid); no batch scratch, no statistics.
+constexpr int64_t kRetryNever = -1;
+constexpr int64_t kRetryInvalid = -2;
+struct RetryArgs {
+    const uint64_t* key;
+    const int32_t* permits;
+    const int64_t* now_ns;
+    const uint16_t* limiter;       // nullable: limiter 0
+    const uint8_t* skip;           // nullable; skip[i] != 0: wait 0, no table access
+    int64_t* wait_ms;
+    const DevLimiter* lims;
+    uint32_t n, n_lim;
+    int shard_bits;
+    unsigned long long* dbg;       // measurement builds (RL_RETRY_COUNT): {searches, bisections,
+                                   // buckets probed}
+};
+hipError_t launch_retry_after(const RetryArgs& a, hipStream_t s);
 hipError_t launch_owner_partition(const uint64_t* key, uint32_t n, uint32_t shard_count,
                                   uint32_t* perm, uint32_t* counts_dev, uint32_t* scratch,
                                   const DirSlot* dir, hipStream_t s);

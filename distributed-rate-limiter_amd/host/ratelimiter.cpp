@@ -65,6 +65,12 @@ int GpuEngine::executeBatch(size_t n, const uint64_t* key, const int32_t* permit
     return st;
 }
 
+int GpuEngine::retryAfter(size_t n, const uint64_t* key, const int32_t* permits, const int64_t* now,
+                          const uint16_t* limiter, const uint8_t* skip, int64_t* waitMs) {
+    std::lock_guard<std::mutex> lk(mu_);
+    return rl_retry_after(e_, n, key, permits, now, limiter, skip, waitMs);
+}
+
 GpuRateLimiter::GpuRateLimiter(std::shared_ptr<GpuEngine> engine, Algorithm algo,
                                const RateLimitConfig& cfg, Clock clock, int batchWindowMicros)
     : allowedRequests(algo == Algorithm::TokenBucket ? "ratelimiter.tokenbucket.allowed"
@@ -168,8 +174,12 @@ void GpuRateLimiter::flushLocked(std::unique_lock<std::mutex>& lk) {
     }
 }
 
-bool GpuRateLimiter::tryAcquire(const std::string& key, int permits) {
+void GpuRateLimiter::requirePositive(int permits) {
     if (permits <= 0) throw IllegalArgumentException("permits must be positive");  // :87-89 / :106-108
+}
+
+bool GpuRateLimiter::tryAcquire(const std::string& key, int permits) {
+    requirePositive(permits);
     Pending p{keyHash(key), permits, 0, RL_OP_ACQUIRE};
     submit(p);
     if (p.allowed) allowedRequests.increment();
@@ -186,6 +196,32 @@ int64_t GpuRateLimiter::getAvailablePermits(const std::string& key) {
 void GpuRateLimiter::reset(const std::string& key) {
     Pending p{keyHash(key), 1, 0, RL_OP_RESET};
     submit(p);
+}
+
+int64_t GpuRateLimiter::retryAfterMillis(const std::string& key, int permits) {
+    requirePositive(permits);
+    const uint64_t k = keyHash(key);
+    const int32_t p = permits;
+    int64_t now = 0, wait = 0;
+    int st;
+    {
+        // behind every tryAcquire that has returned: wait out a flush in progress and hold
+        // the flush slot while the query runs (as tryAcquireBatch does); the clock is read
+        // under mu_, like a request's
+        std::unique_lock<std::mutex> lk(mu_);
+        cv_.wait(lk, [&] { return !flushing_; });
+        flushing_ = true;
+        now = clock_();
+        lk.unlock();
+        st = engine_->retryAfter(1, &k, &p, &now, &id_, nullptr, &wait);
+        lk.lock();
+        flushing_ = false;
+        cv_.notify_all();
+    }
+    checkStatus(st, "retryAfterMillis");
+    if (st == RL_E_INVALID_REQUEST || wait == RL_RETRY_INVALID)
+        throw IllegalArgumentException("retryAfterMillis: invalid request");
+    return wait;                                     // RL_RETRY_NEVER = -1: never
 }
 
 void GpuRateLimiter::tryAcquireBatch(size_t n, const uint64_t* keyHash, const int32_t* permits,

@@ -120,6 +120,9 @@ class GpuEngine {
     int executeBatch(size_t n, const uint64_t* key, const int32_t* permits, const int64_t* now,
                      const uint16_t* limiter, const uint8_t* op, uint8_t* allowed,
                      int64_t* remaining, uint64_t* cacheHits);
+    // rl_retry_after: ms until an acquire would be allowed (read-only; skip nullable).
+    int retryAfter(size_t n, const uint64_t* key, const int32_t* permits, const int64_t* now,
+                   const uint16_t* limiter, const uint8_t* skip, int64_t* waitMs);
 
   private:
     rl_engine* e_ = nullptr;
@@ -147,6 +150,16 @@ class GpuRateLimiter : public RateLimiter {
     bool tryAcquire(const std::string& key, int permits) override;
     int64_t getAvailablePermits(const std::string& key) override;
     void reset(const std::string& key) override;
+
+    // Milliseconds, from the clock's now, until tryAcquire(key, permits) would be allowed on the
+    // key's state as it stands (0: now; -1: never, permits > maxPermits): what a caller puts
+    // into Retry-After / X-RateLimit-Reset beside a 429 (the reference's
+    // DemoController.rateLimitExceeded). Not part of the reference's RateLimiter interface.
+    // Read-only; it sees every tryAcquire of this object that has returned.
+    int64_t retryAfterMillis(const std::string& key, int permits = 1);
+    // the reference's permits check (SlidingWindowRateLimiter.java:87-89,
+    // TokenBucketRateLimiter.java:106-108): throws IllegalArgumentException for permits <= 0
+    static void requirePositive(int permits);
 
     // tryAcquireBatch(keys[], permits[], nowNanos[]); remaining may be null.
     void tryAcquireBatch(size_t n, const uint64_t* keyHash, const int32_t* permits,

@@ -30,6 +30,7 @@ RL_E_INTERNAL = -8      # engine logic error (include/rl_engine.h)
 SW, TB = 0, 1
 OP_ACQUIRE, OP_PEEK, OP_RESET = 0, 1, 2
 REM_UNKNOWN, REM_INVALID, REM_ERROR = -1, -2, -3
+RETRY_NEVER, RETRY_INVALID = -1, -2   # RL_RETRY_* (rl_retry_after)
 OPT_STAGE_TIMING = 1
 OPT_PIPELINE = 2       # RL_OPT_PIPELINE: partition of batch k+1 overlaps batch k's decisions
 OPT_FIXED_CAPACITY = 4  # RL_OPT_FIXED_CAPACITY: no on-demand table growth
@@ -50,6 +51,7 @@ EXPORTS = [
     "rl_owner_of_engine", "rl_router_create", "rl_router_step", "rl_router_finish",
     "rl_router_plan_directory", "rl_router_destroy", "rl_pin_host", "rl_unpin_host",
     "rl_grow_limiter", "rl_limiter_slots", "rl_router_create_ex", "rl_router_stats_get",
+    "rl_retry_after", "rl_retry_after_device",
 ]
 RCCL_EXPORTS = ["rl_rccl_unique_id", "rl_transport_rccl_create", "rl_transport_rccl_destroy"]
 STATE_SW_BUCKET, STATE_TB_BUCKET = 0, 1
@@ -171,6 +173,8 @@ def lib():
     L.rl_grow_limiter.argtypes = [vp, u16, ctypes.c_uint64]
     L.rl_limiter_slots.argtypes = [vp, u16, ctypes.POINTER(ctypes.c_uint64)]
     L.rl_unpin_host.argtypes = [vp, vp]
+    L.rl_retry_after.argtypes = [vp, sz] + [vp] * 6
+    L.rl_retry_after_device.argtypes = [vp, sz] + [vp] * 7
     L.rl_owner_of_engine.restype = u32
     _lib = L
     return L
@@ -343,6 +347,32 @@ class Engine:
         keys = np.ascontiguousarray(keys, np.uint64)
         now_ns = np.ascontiguousarray(now_ns, np.int64)
         return self._L.rl_reset(self._h, int(limiter), keys.shape[0], _p(keys), _p(now_ns))
+
+    def retry_after(self, limiter, keys, permits, now_ns, skip=None):
+        """Milliseconds until an acquire of permits[i] on keys[i] would be allowed, from now_ns[i]
+        (rl_retry_after): 0 = now, RETRY_NEVER, RETRY_INVALID. `limiter` is one id or an array;
+        permits and now_ns broadcast; skip[i] != 0 answers 0 without a lookup (a batch's
+        `allowed`). Read-only. Returns (wait_ms int64 array, status)."""
+        keys = np.ascontiguousarray(keys, np.uint64)
+        n = keys.shape[0]
+        permits = np.ascontiguousarray(np.broadcast_to(np.asarray(permits, np.int32), (n,)))
+        now_ns = np.ascontiguousarray(np.broadcast_to(np.asarray(now_ns, np.int64), (n,)))
+        limiter = np.ascontiguousarray(np.broadcast_to(np.asarray(limiter, np.uint16), (n,)))
+        skip = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+        wait = np.zeros(n, np.int64)
+        st = self._L.rl_retry_after(self._h, n, _p(keys), _p(permits), _p(now_ns), _p(limiter),
+                                    _p(skip), _p(wait))
+        if st not in (RL_OK, RL_E_INVALID_REQUEST):
+            raise RlError(st, "rl_retry_after")
+        return wait, st
+
+    def retry_after_device(self, n, keys, permits, now_ns, limiter, skip, wait, stream=None):
+        """rl_retry_after_device on device buffers (torch tensors or raw pointers; limiter and
+        skip may be None); asynchronous, ordered behind the batches submitted before it."""
+        st = self._L.rl_retry_after_device(self._h, n, _p(keys), _p(permits), _p(now_ns),
+                                           _p(limiter), _p(skip), _p(wait), _p(stream))
+        if st != RL_OK:
+            raise RlError(st, "rl_retry_after_device")
 
     def export_state(self, now_ns):
         """Live state at now_ns in the Redis layout: a STATE_DTYPE array (rl_export_state)."""

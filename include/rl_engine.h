@@ -220,6 +220,37 @@ int  rl_available(rl_engine* e, uint16_t limiter, size_t n, const uint64_t* key_
 int  rl_reset(rl_engine* e, uint16_t limiter, size_t n, const uint64_t* key_hash,
               const int64_t* now_ns);
 
+/* ---- retry-after for denied acquires ------------------------------------------
+ * For query i = (limiter, key_hash, permits, now_ns) with now = floorDiv(now_ns, 1e6) and S the
+ * key's state when the call runs (after every batch submitted before it), let P(t) be
+ * "tryAcquire(key, permits) at millisecond t is allowed on S" (not applied; with
+ * RL_LIM_LOCAL_CACHE the local cache's rejecting entry counts). Then
+ *   wait_ms[i] = min{ t >= now : P(t) } - now      (0: allowed right now; an absent or expired
+ *                                                   key gives 0 for any permits <= maxPermits)
+ *              = RL_RETRY_NEVER    permits > maxPermits (TokenBucketRateLimiter.java:110-116;
+ *                                  a sliding window's estimate is never negative)
+ *              = RL_RETRY_INVALID  permits <= 0 or unknown limiter (the host-buffer call then
+ *                                  returns RL_E_INVALID_REQUEST; the other queries are answered)
+ * exactly: the engine's own decision code evaluates P. wait_ms <= 2 * window_ms +
+ * local_cache_ttl_ms + 1. skip[i] != 0 gives wait_ms[i] = 0 without a table access, so a
+ * batch's own arrays and its `allowed` output can be handed straight back and only the
+ * denials cost a lookup. The call changes nothing: no state, no cache entry, no batch
+ * statistic, not the status rl_last_status reports. A sliding-window query whose now lies
+ * before the key's newest INCR (time regression) is searched from that INCR's time; its wait
+ * still counts from now. Multi-GPU: ask the key's owner, as with the batch calls.
+ * `limiter` and `skip` may be NULL (limiter 0, nothing skipped). */
+#define RL_RETRY_NEVER   (-1)
+#define RL_RETRY_INVALID (-2)
+int  rl_retry_after(rl_engine* e, size_t n, const uint64_t* key_hash, const int32_t* permits,
+                    const int64_t* now_ns, const uint16_t* limiter, const uint8_t* skip,
+                    int64_t* wait_ms);
+/* The same on DEVICE buffers, enqueued on `stream` (NULL = the engine's stream) behind every
+ * batch submitted before it; returns launch / argument status only. */
+int  rl_retry_after_device(rl_engine* e, size_t n, const uint64_t* key_hash,
+                           const int32_t* permits, const int64_t* now_ns,
+                           const uint16_t* limiter, const uint8_t* skip,
+                           int64_t* wait_ms, void* stream);
+
 /* Observability. */
 int  rl_batch_stats_get(rl_engine* e, rl_batch_stats* out);
 /* Milliseconds of each pipeline stage of the last batch (needs RL_OPT_STAGE_TIMING);
