@@ -191,6 +191,7 @@ struct rl_engine {
     uint32_t inject_fail = 0;               // rl_tune("fail_batches"): tests of callers' error paths
     uint64_t grows = 0;                     // region-count doublings done (rl_batch_stats)
     unsigned long long* retry_dbg = nullptr; // measurement builds (RL_RETRY_COUNT): k_retry_after's counters
+    void* topk = nullptr;                   // rl_top_keys scratch (topk_scratch_bytes), on first use
 };
 
 #define HIP_OK(x)                                                      \
@@ -353,7 +354,7 @@ extern "C" void rl_destroy(rl_engine* e) {
     dfree(e->walk_tab);
     dfree(e->route_list); dfree(e->route_start); dfree(e->route_cnt);
     dfree(e->order); dfree(e->order_meta); dfree(e->solo_list);
-    dfree(e->d_stats); dfree(e->retry_dbg);
+    dfree(e->d_stats); dfree(e->retry_dbg); dfree(e->topk);
     dfree(e->s_key); dfree(e->s_permits); dfree(e->s_now); dfree(e->s_lim); dfree(e->s_op);
     dfree(e->s_allowed); dfree(e->s_remaining); dfree(e->s_tokens);
     dfree(e->route_scratch); dfree(e->route_counts); dfree(e->d_dir);
@@ -1211,6 +1212,101 @@ extern "C" int rl_retry_after(rl_engine* e, size_t n, const uint64_t* key_hash, 
     HIP_OK(hipStreamSynchronize(s));
     for (size_t i = 0; i < n; ++i)
         if (wait_ms[i] == RL_RETRY_INVALID) return RL_E_INVALID_REQUEST;
+    return RL_OK;
+}
+
+// ---------------------------------------------------------------- heavy-hitter keys
+// rl_topk.hip on the engine stream: clear, the sketch pass and the filter pass over the keys
+// (the host form: over every staged chunk), compact + select. Nothing here touches a limiter
+// table, the batch scratch, d_stats, d_ctl or the status bookkeeping.
+static_assert(RL_TOP_KEYS_MAX == kTopkMax && RL_TOP_KEYS_MAX == kDirMax, "top keys = directory capacity");
+static_assert(RL_TOP_KEYS_CANDIDATES == kTopkCandidates, "candidate cap");
+constexpr uint64_t kTopkMaxN = 1ULL << 31;
+
+static bool topk_args_ok(rl_engine* e, size_t n, const uint64_t* key_hash, uint32_t k, uint64_t min_count) {
+    return e && (n == 0 || key_hash) && k != 0 && k <= RL_TOP_KEYS_MAX && min_count != 0 &&
+           (uint64_t)n <= kTopkMaxN;
+}
+
+static int topk_scratch(rl_engine* e, TopkScratch* sc) {
+    if (!e->topk) {
+        int rc = dalloc(&e->topk, topk_scratch_bytes());
+        if (rc != RL_OK) return rc;
+    }
+    *sc = topk_scratch_at(e->topk);
+    return RL_OK;
+}
+
+extern "C" int rl_top_keys_device(rl_engine* e, size_t n, const uint64_t* key_hash, uint32_t k,
+                                  uint64_t min_count, uint64_t* top_key, uint64_t* top_count,
+                                  uint64_t* hdr, void* stream) {
+    if (!topk_args_ok(e, n, key_hash, k, min_count) || !top_key || !top_count || !hdr)
+        return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipSetDevice(e->device);
+    TopkScratch sc;
+    int rc = topk_scratch(e, &sc);
+    if (rc != RL_OK) return rc;
+    hipStream_t user = (hipStream_t)stream;
+    const bool cross = user && user != e->stream;
+    hipEvent_t ev = nullptr;
+    if (cross) {
+        // order the engine stream after the caller's work, and the caller's after ours
+        HIP_OK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        hipError_t he = hipEventRecord(ev, user);
+        if (he == hipSuccess) he = hipStreamWaitEvent(e->stream, ev, 0);
+        if (he != hipSuccess) { (void)hipEventDestroy(ev); return RL_E_DEVICE; }
+    }
+    hipStream_t s = e->stream;
+    hipError_t he = launch_topk_clear(sc, s);
+    if (he == hipSuccess) he = launch_topk_pass(sc, 0, key_hash, (uint32_t)n, min_count, s);
+    if (he == hipSuccess) he = launch_topk_pass(sc, 1, key_hash, (uint32_t)n, min_count, s);
+    if (he == hipSuccess) he = launch_topk_select(sc, k, min_count, n, top_key, top_count, hdr, s);
+    if (cross) {
+        if (he == hipSuccess) he = hipEventRecord(ev, s);
+        if (he == hipSuccess) he = hipStreamWaitEvent(user, ev, 0);
+        (void)hipEventDestroy(ev);
+    }
+    return he == hipSuccess ? RL_OK : RL_E_DEVICE;
+}
+
+extern "C" int rl_top_keys(rl_engine* e, size_t n, const uint64_t* key_hash, uint32_t k,
+                           uint64_t min_count, uint64_t* top_key, uint64_t* top_count, size_t* n_out,
+                           uint64_t* n_heavy) {
+    if (!topk_args_ok(e, n, key_hash, k, min_count) || !top_key || !top_count || !n_out || !n_heavy)
+        return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipSetDevice(e->device);
+    TopkScratch sc;
+    int rc = topk_scratch(e, &sc);
+    if (rc != RL_OK) return rc;
+    // chunks of the staging buffers' size (at most max_batch keys, as the batch calls leave
+    // them); every chunk is uploaded once per pass
+    const size_t chunk = std::min<size_t>(std::max<size_t>(n, 1), (size_t)e->opts.max_batch);
+    rc = ensure_staging(e, chunk);
+    if (rc != RL_OK) return rc;
+    hipStream_t s = e->stream;
+    HIP_OK(launch_topk_clear(sc, s));
+    for (int pass = 0; pass < 2; ++pass)
+        for (size_t at = 0; at < n; at += chunk) {
+            const size_t m = std::min(chunk, n - at);
+            HIP_OK(hipMemcpyAsync(e->s_key, key_hash + at, m * 8, hipMemcpyHostToDevice, s));
+            HIP_OK(launch_topk_pass(sc, pass, e->s_key, (uint32_t)m, min_count, s));
+        }
+    HIP_OK(launch_topk_select(sc, k, min_count, n, sc.out_key, sc.out_cnt, sc.out_hdr, s));
+    uint64_t hdr[4] = {0, 0, 0, 0};
+    HIP_OK(hipMemcpyAsync(hdr, sc.out_hdr, sizeof(hdr), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    *n_out = 0;
+    *n_heavy = 0;
+    if (hdr[2]) return RL_E_CAPACITY;
+    if (hdr[0] > k) return RL_E_INTERNAL;
+    if (hdr[0]) {
+        HIP_OK(hipMemcpy(top_key, sc.out_key, hdr[0] * 8, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(top_count, sc.out_cnt, hdr[0] * 8, hipMemcpyDeviceToHost));
+    }
+    *n_out = (size_t)hdr[0];
+    *n_heavy = hdr[1];
     return RL_OK;
 }
 

@@ -430,6 +430,42 @@ struct RetryArgs {
                                    // buckets probed}
 };
 hipError_t launch_retry_after(const RetryArgs& a, hipStream_t s);
+// Heavy-hitter keys of a key stream (rl_topk.hip): a two-row count sketch, an exact
+// {key, count} table of the keys the sketch lets through, a dense list of those that qualify,
+// and the sorted answer. One scratch of fixed size (topk_scratch_bytes) holds all of it.
+constexpr uint32_t kTopkMax = 4096;              // RL_TOP_KEYS_MAX = kDirMax
+constexpr uint32_t kTopkCandidates = 65536;      // RL_TOP_KEYS_CANDIDATES
+constexpr uint32_t kTopkSketchCells = 1u << 22;  // per row, two rows
+constexpr uint32_t kTopkTableSlots = 1u << 19;   // open-addressed, at most kTopkStoreMax live
+constexpr uint32_t kTopkStoreMax = 1u << 18;     // keys the sketch may let through
+struct TopkCtl {
+    uint32_t live;                 // keys in the table (and the key ~0, counted in `special`)
+    uint32_t overflow;             // more than kTopkStoreMax keys passed the sketch, or more than
+                                   // kTopkCandidates qualify
+    uint32_t special;              // occurrences of the key ~0 (the tables' empty mark)
+    uint32_t heavy;                // keys that qualify = n_heavy (the list holds them)
+    uint32_t pad[12];
+};
+struct TopkScratch {
+    TopkCtl* ctl;
+    uint32_t* sketch;              // [2][kTopkSketchCells]
+    uint64_t* tab_key;             // [kTopkTableSlots], ~0 = empty
+    uint32_t* tab_cnt;             // [kTopkTableSlots]
+    uint64_t* list_key;            // [kTopkCandidates]
+    uint32_t* list_cnt;            // [kTopkCandidates]
+    uint64_t* out_key;             // [kTopkMax] the host form's device-side outputs
+    uint64_t* out_cnt;             // [kTopkMax]
+    uint64_t* out_hdr;             // [4]
+};
+size_t topk_scratch_bytes();
+TopkScratch topk_scratch_at(void* base);
+hipError_t launch_topk_clear(const TopkScratch& sc, hipStream_t s);
+// pass 0: sketch; pass 1: filter and exact count (after every chunk's pass 0)
+hipError_t launch_topk_pass(const TopkScratch& sc, int pass, const uint64_t* key, uint32_t n,
+                            uint64_t min_count, hipStream_t s);
+// compact + select: writes top_key / top_count [0, n_out) and hdr = {n_out, n_heavy, overflow, n}
+hipError_t launch_topk_select(const TopkScratch& sc, uint32_t k, uint64_t min_count, uint64_t n,
+                              uint64_t* top_key, uint64_t* top_count, uint64_t* hdr, hipStream_t s);
 hipError_t launch_owner_partition(const uint64_t* key, uint32_t n, uint32_t shard_count,
                                   uint32_t* perm, uint32_t* counts_dev, uint32_t* scratch,
                                   const DirSlot* dir, hipStream_t s);

@@ -500,3 +500,46 @@ extern "C" int rl_router_plan_directory(rl_router* r, size_t n, const uint64_t* 
     if (rc == RL_OK && placed) *placed = (uint32_t)dk.size();
     return rc;
 }
+
+extern "C" int rl_router_plan_directory_sampled(rl_router* r, size_t n, const uint64_t* key_hash,
+                                                uint32_t k, uint64_t min_count, uint32_t* placed,
+                                                void* stream) {
+    // argument errors, as rl_router_plan_directory's, return before the collective (every
+    // rank passes the same k and min_count)
+    if (!r || (n && !key_hash) || k == 0 || k > kDirMax || min_count == 0 || (uint64_t)n > (1ULL << 31))
+        return RL_E_INVALID_ARG;
+    hipStream_t s = stream ? (hipStream_t)stream : r->own;
+    // this rank's candidates land in the exchange buffer, which the plan below rewrites only
+    // after they are on the host: keys and counts where it puts its candidates ([2 kDirMax]),
+    // the header at the start of the receive area
+    uint64_t* dk = r->dir + 4 * (size_t)r->world;
+    uint64_t* dc = dk + kDirMax;
+    uint64_t* dh = dc + kDirMax;
+    uint64_t hdr[4] = {0, 0, 0, 0};
+    std::vector<uint64_t> key, cnt;
+    // a failure of this rank alone must not leave the others waiting in the collective: it
+    // goes on with no candidates and reports afterwards
+    int mine = rl_top_keys_device(r->e, n, key_hash, k, min_count, dk, dc, dh, s);
+    if (mine == RL_OK) {
+        if (hipMemcpyAsync(hdr, dh, sizeof(hdr), hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess)
+            mine = RL_E_DEVICE;
+        else if (hdr[2])
+            mine = RL_E_CAPACITY;
+        else if (hdr[0] > kDirMax)
+            mine = RL_E_INTERNAL;
+    }
+    if (mine == RL_OK && hdr[0]) {
+        key.resize(hdr[0]);
+        cnt.resize(hdr[0]);
+        if (hipMemcpy(key.data(), dk, hdr[0] * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(cnt.data(), dc, hdr[0] * 8, hipMemcpyDeviceToHost) != hipSuccess) {
+            mine = RL_E_DEVICE;
+            key.clear();
+            cnt.clear();
+        }
+    }
+    const int rc = rl_router_plan_directory(r, key.size(), key.data(), cnt.data(), (uint64_t)n, k,
+                                            placed, s);
+    return mine != RL_OK ? mine : rc;
+}

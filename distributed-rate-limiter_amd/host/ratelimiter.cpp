@@ -71,6 +71,25 @@ int GpuEngine::retryAfter(size_t n, const uint64_t* key, const int32_t* permits,
     return rl_retry_after(e_, n, key, permits, now, limiter, skip, waitMs);
 }
 
+std::vector<std::pair<uint64_t, uint64_t>> GpuEngine::topKeys(const uint64_t* hashes, size_t n, uint32_t k,
+                                                              uint64_t minCount) {
+    if (k == 0 || k > RL_TOP_KEYS_MAX || minCount == 0 || (n && !hashes))
+        throw IllegalArgumentException("topKeys: k in [1, RL_TOP_KEYS_MAX], minCount >= 1");
+    std::vector<uint64_t> key(k), cnt(k);
+    size_t nOut = 0;
+    uint64_t nHeavy = 0;
+    int st;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        st = rl_top_keys(e_, n, hashes, k, minCount, key.data(), cnt.data(), &nOut, &nHeavy);
+    }
+    if (st == RL_E_INVALID_ARG) throw IllegalArgumentException(std::string("topKeys: ") + rl_strerror(st));
+    if (st != RL_OK) throw StorageException(std::string("topKeys: ") + rl_strerror(st), st);
+    std::vector<std::pair<uint64_t, uint64_t>> out(nOut);
+    for (size_t i = 0; i < nOut; ++i) out[i] = {key[i], cnt[i]};
+    return out;
+}
+
 GpuRateLimiter::GpuRateLimiter(std::shared_ptr<GpuEngine> engine, Algorithm algo,
                                const RateLimitConfig& cfg, Clock clock, int batchWindowMicros)
     : allowedRequests(algo == Algorithm::TokenBucket ? "ratelimiter.tokenbucket.allowed"

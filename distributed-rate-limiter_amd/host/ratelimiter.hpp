@@ -22,6 +22,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/rl_engine.h"
@@ -123,6 +124,12 @@ class GpuEngine {
     // rl_retry_after: ms until an acquire would be allowed (read-only; skip nullable).
     int retryAfter(size_t n, const uint64_t* key, const int32_t* permits, const int64_t* now,
                    const uint16_t* limiter, const uint8_t* skip, int64_t* waitMs);
+    // rl_top_keys: the (key hash, count) pairs of the at most k most frequent of the hashes
+    // that occur at least minCount times, count descending then hash ascending; exact.
+    // Throws StorageException when the sample overflows the engine's candidate store
+    // (RL_E_CAPACITY), IllegalArgumentException for k == 0, k > RL_TOP_KEYS_MAX, minCount == 0.
+    std::vector<std::pair<uint64_t, uint64_t>> topKeys(const uint64_t* hashes, size_t n, uint32_t k,
+                                                       uint64_t minCount);
 
   private:
     rl_engine* e_ = nullptr;

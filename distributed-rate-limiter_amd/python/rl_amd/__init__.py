@@ -31,6 +31,7 @@ SW, TB = 0, 1
 OP_ACQUIRE, OP_PEEK, OP_RESET = 0, 1, 2
 REM_UNKNOWN, REM_INVALID, REM_ERROR = -1, -2, -3
 RETRY_NEVER, RETRY_INVALID = -1, -2   # RL_RETRY_* (rl_retry_after)
+TOP_KEYS_MAX, TOP_KEYS_CANDIDATES = 4096, 65536   # RL_TOP_KEYS_* (rl_top_keys)
 OPT_STAGE_TIMING = 1
 OPT_PIPELINE = 2       # RL_OPT_PIPELINE: partition of batch k+1 overlaps batch k's decisions
 OPT_FIXED_CAPACITY = 4  # RL_OPT_FIXED_CAPACITY: no on-demand table growth
@@ -52,6 +53,7 @@ EXPORTS = [
     "rl_router_plan_directory", "rl_router_destroy", "rl_pin_host", "rl_unpin_host",
     "rl_grow_limiter", "rl_limiter_slots", "rl_router_create_ex", "rl_router_stats_get",
     "rl_retry_after", "rl_retry_after_device",
+    "rl_top_keys", "rl_top_keys_device", "rl_router_plan_directory_sampled",
 ]
 RCCL_EXPORTS = ["rl_rccl_unique_id", "rl_transport_rccl_create", "rl_transport_rccl_destroy"]
 STATE_SW_BUCKET, STATE_TB_BUCKET = 0, 1
@@ -175,6 +177,11 @@ def lib():
     L.rl_unpin_host.argtypes = [vp, vp]
     L.rl_retry_after.argtypes = [vp, sz] + [vp] * 6
     L.rl_retry_after_device.argtypes = [vp, sz] + [vp] * 7
+    L.rl_top_keys.argtypes = [vp, sz, vp, u32, ctypes.c_uint64, vp, vp, ctypes.POINTER(sz),
+                              ctypes.POINTER(ctypes.c_uint64)]
+    L.rl_top_keys_device.argtypes = [vp, sz, vp, u32, ctypes.c_uint64, vp, vp, vp, vp]
+    L.rl_router_plan_directory_sampled.argtypes = [vp, sz, vp, u32, ctypes.c_uint64,
+                                                   ctypes.POINTER(u32), vp]
     L.rl_owner_of_engine.restype = u32
     _lib = L
     return L
@@ -373,6 +380,44 @@ class Engine:
                                            _p(limiter), _p(skip), _p(wait), _p(stream))
         if st != RL_OK:
             raise RlError(st, "rl_retry_after_device")
+
+    def top_keys(self, keys, k, min_count):
+        """The keys of a host array that occur at least min_count times, the k most frequent
+        first (count descending, key ascending), exact (rl_top_keys). Returns (keys uint64,
+        counts uint64, n_heavy); raises RlError(RL_E_CAPACITY) when the sample overflows."""
+        keys = np.ascontiguousarray(keys, np.uint64)
+        k = int(k)
+        top = np.zeros(max(min(k, TOP_KEYS_MAX), 0), np.uint64)
+        cnt = np.zeros_like(top)
+        n_out = ctypes.c_size_t(0)
+        n_heavy = ctypes.c_uint64(0)
+        st = self._L.rl_top_keys(self._h, keys.shape[0], _p(keys) if keys.shape[0] else None, k,
+                                 int(min_count), _p(top), _p(cnt), ctypes.byref(n_out),
+                                 ctypes.byref(n_heavy))
+        if st != RL_OK:
+            raise RlError(st, "rl_top_keys")
+        return top[:n_out.value], cnt[:n_out.value], n_heavy.value
+
+    def top_keys_device(self, keys, k, min_count, stream=None):
+        """rl_top_keys_device on a device tensor of key hashes (8-byte integers). Returns
+        (keys, counts, n_heavy): two device tensors of n_out 64-bit words holding unsigned
+        values (torch.uint64 views) and an int; reads the header back, so it synchronises.
+        Raises RlError(RL_E_CAPACITY) when the sample overflows."""
+        import torch
+        assert keys.element_size() == 8 and keys.is_contiguous()
+        k = int(k)
+        top = torch.zeros(max(min(k, TOP_KEYS_MAX), 1), dtype=torch.int64, device=keys.device)
+        cnt = torch.zeros_like(top)
+        hdr = torch.zeros(4, dtype=torch.int64, device=keys.device)
+        st = self._L.rl_top_keys_device(self._h, keys.numel(), _p(keys) if keys.numel() else None, k,
+                                        int(min_count), _p(top), _p(cnt), _p(hdr), _p(stream))
+        if st != RL_OK:
+            raise RlError(st, "rl_top_keys_device")
+        self.sync()
+        n_out, n_heavy, overflow, _ = (int(x) for x in hdr.cpu())
+        if overflow:
+            raise RlError(RL_E_CAPACITY, "rl_top_keys_device")
+        return top[:n_out].view(torch.uint64), cnt[:n_out].view(torch.uint64), n_heavy
 
     def export_state(self, now_ns):
         """Live state at now_ns in the Redis layout: a STATE_DTYPE array (rl_export_state)."""

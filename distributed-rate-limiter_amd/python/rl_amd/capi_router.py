@@ -190,6 +190,20 @@ class CRouter:
             raise rl_amd.RlError(st, "rl_router_plan_directory")
         return placed.value
 
+    def plan_directory_sampled(self, keys, k: int, min_count: int, stream=None) -> int:
+        """Hot-key directory from a device tensor of this rank's sampled key hashes
+        (collective, rl_router_plan_directory_sampled): the engine finds the rank's top keys
+        itself. Raises RlError(RL_E_CAPACITY) on a rank whose sample overflowed, after the
+        collective (the directory is installed all the same)."""
+        placed = ctypes.c_uint32(0)
+        n = int(keys.numel())
+        st = self._L.rl_router_plan_directory_sampled(self._h, n, rl_amd._p(keys) if n else None,
+                                                      int(k), int(min_count), ctypes.byref(placed),
+                                                      rl_amd._p(stream))
+        if st != rl_amd.RL_OK:
+            raise rl_amd.RlError(st, "rl_router_plan_directory_sampled")
+        return placed.value
+
     def stats(self) -> dict:
         st = RouterStats()
         self._L.rl_router_stats_get(self._h, ctypes.byref(st))

@@ -251,6 +251,41 @@ int  rl_retry_after_device(rl_engine* e, size_t n, const uint64_t* key_hash,
                            const uint16_t* limiter, const uint8_t* skip,
                            int64_t* wait_ms, void* stream);
 
+/* ---- heavy-hitter keys of a key stream ------------------------------------------
+ * The candidates rl_router_plan_directory asks for, computed on the device: with
+ * c(h) = #{ i < n : key_hash[i] == h } and H = { h : c(h) >= min_count }, ordered by c
+ * descending and then key_hash ascending as an unsigned 64-bit value,
+ *   n_heavy = |H| (exact, also when it exceeds k),  n_out = min(k, n_heavy),
+ *   top_key / top_count [0, n_out) = the first n_out elements of H with their exact counts;
+ * entries at and beyond n_out are left untouched. Ties at the cut are broken by that order, so
+ * the answer is unique. Every 64-bit value is a legal key, 0 and ~0 included. There is no
+ * approximate mode: a result reported without overflow is exact.
+ * RL_E_INVALID_ARG, before any device call and with every output untouched: a null engine,
+ * n > 0 with a null key_hash, a null output pointer, k == 0, k > RL_TOP_KEYS_MAX,
+ * min_count == 0, n > 2^31. n == 0 is valid (n_out = n_heavy = 0).
+ * Overflow: a count sketch (2 rows of 2^22 cells) drops the keys that cannot reach min_count,
+ * and the others, up to 4 x RL_TOP_KEYS_CANDIDATES of them, are counted exactly. The call
+ * reports overflow when n_heavy > RL_TOP_KEYS_CANDIDATES (always) or when more keys than the
+ * store holds pass the sketch; never when the sample has at most RL_TOP_KEYS_CANDIDATES
+ * distinct keys. The host form then returns RL_E_CAPACITY with *n_out = *n_heavy = 0 (raise
+ * min_count or sample less).
+ * Both forms only read: no limiter state, batch statistic or rl_last_status changes. Their
+ * scratch (38.8 MiB, whatever n is) is allocated by the first call and freed by rl_destroy.
+ * One top-keys call may be in flight per engine.
+ * The host form stages key_hash through the engine's staging buffers in chunks of at most
+ * rl_opts.max_batch keys (n itself is not bounded by it) and synchronises. */
+#define RL_TOP_KEYS_MAX        4096    /* = the owner directory's capacity                */
+#define RL_TOP_KEYS_CANDIDATES 65536   /* most keys that may qualify in one call          */
+int  rl_top_keys(rl_engine* e, size_t n, const uint64_t* key_hash, uint32_t k, uint64_t min_count,
+                 uint64_t* top_key, uint64_t* top_count, size_t* n_out, uint64_t* n_heavy);
+/* The same on DEVICE buffers (key_hash [n], top_key / top_count [k], hdr [4]), enqueued on
+ * `stream` (NULL = the engine's stream) without a host synchronisation; returns argument /
+ * launch status only. hdr = { n_out, n_heavy, overflow, n }; on overflow { 0, 0, 1, n } and
+ * top_key / top_count untouched. */
+int  rl_top_keys_device(rl_engine* e, size_t n, const uint64_t* key_hash, uint32_t k,
+                        uint64_t min_count, uint64_t* top_key, uint64_t* top_count, uint64_t* hdr,
+                        void* stream);
+
 /* Observability. */
 int  rl_batch_stats_get(rl_engine* e, rl_batch_stats* out);
 /* Milliseconds of each pipeline stage of the last batch (needs RL_OPT_STAGE_TIMING);
@@ -466,13 +501,22 @@ int  rl_router_step(rl_router* r, size_t n, const uint64_t* key_hash, const int3
 /* Collective: the worst status of every rank's last batches (all ranks get the same). */
 int  rl_router_finish(rl_router* r);
 /* Hot-key directory for the whole router (collective, before any state exists for the
- * chosen keys): each rank passes its n candidates with their request counts (e.g. the top
+ * chosen keys): each rank passes its n candidates (HOST arrays) with their request counts (e.g. the top
  * keys of a sample of its traffic) and the total it sampled; the router merges them, keeps
  * the k hottest and places them on owners by longest-processing-time-first over the
  * owners' expected loads (rl_set_owner_directory on every rank). *placed = keys listed. */
 int  rl_router_plan_directory(rl_router* r, size_t n, const uint64_t* key_hash,
                               const uint64_t* count, uint64_t sampled, uint32_t k,
                               uint32_t* placed, void* stream);
+/* The same with the candidates taken from a DEVICE sample of this rank's traffic (collective):
+ * rl_top_keys_device(n, key_hash, k, min_count) on the rank's engine, its at most
+ * RL_TOP_KEYS_MAX results copied to the host, then rl_router_plan_directory with them and
+ * sampled = n. A rank whose sample overflowed (RL_TOP_KEYS_CANDIDATES) contributes no
+ * candidates, completes the collective and then returns RL_E_CAPACITY; every rank still
+ * installs the same directory. */
+int  rl_router_plan_directory_sampled(rl_router* r, size_t n, const uint64_t* key_hash,
+                                      uint32_t k, uint64_t min_count, uint32_t* placed,
+                                      void* stream);
 void rl_router_destroy(rl_router* r);
 
 /* ---- synthetic traces (bench / tests; deterministic in (seed, index)) ------ */
