@@ -96,12 +96,15 @@ struct Slot {
 // a slot is FREE iff its four words (and its local-cache word) are all zero; a key is
 // always found before the first free slot of its probe sequence. A slot whose state is
 // dead (no bucket live) but whose words are not all zero is a TOMBSTONE: it keeps the
-// probe chain intact and may be reused by an insert. Writers that load a whole region (a
-// region loaded as an LDS image, the TTL sweep, state import) drop dead slots (written as
-// zeros) and relink or rebuild the chain; sparse region waves (few records) touch single
-// buckets and never create a hole. The only key whose dead state could be all-zero (tag 0 = mix64(0) with
-// a deleted token bucket) is written with c = kDeadMark instead, which no live state has
-// (TB: c bit 0 clear = absent bucket; SW: both counts zero).
+// probe chain intact and may be reused by an insert. The TTL sweep rewrites whole regions: it
+// drops dead slots (written as zeros) and rebuilds the chains; state import and table growth
+// rebuild them too and drop the slots that hold no state at all. A batch's region loaded as an LDS image keeps its dead slots as tombstones where
+// they are, and only once live + dead slots crowd the region (> kTombCrowd, rl_region.hpp)
+// drops them and relinks; sparse region waves (few records) touch single buckets and never
+// create a hole. So used slots = live keys + tombstones (rl_usage.used_slots), and only a
+// sweep brings the two together. The only key whose dead state could be all-zero (tag 0 =
+// mix64(0) with a deleted token bucket) is written with c = kDeadMark instead, which no live
+// state has (TB: c bit 0 clear = absent bucket; SW: both counts zero).
 constexpr uint64_t kDeadMark = 2;
 __host__ __device__ inline bool slot_free(const Slot& v, uint64_t x = 0) {
     return (v.tag | v.a | v.b | v.c | x) == 0;
@@ -116,7 +119,7 @@ __host__ __device__ inline Slot slot_used(Slot v, uint64_t x = 0) {
 constexpr uint32_t kOccUsed = 1u;       // holds a key (live, or a tombstone with kOccTomb)
 constexpr uint32_t kOccTouched = 2u;    // read or written by this batch
 constexpr uint32_t kOccUnloaded = 4u;   // sparse region: bucket not fetched from HBM yet
-constexpr uint32_t kOccTomb = 8u;       // sparse region: dead slot (claimable by an insert)
+constexpr uint32_t kOccTomb = 8u;       // dead slot kept as a tombstone (claimable by an insert)
 constexpr uint32_t kOccDirty = 16u;     // image region: changed by the load (dropped, moved)
 
 // ---------------------------------------------------------------- hashing

@@ -192,6 +192,8 @@ struct rl_engine {
     uint64_t grows = 0;                     // region-count doublings done (rl_batch_stats)
     unsigned long long* retry_dbg = nullptr; // measurement builds (RL_RETRY_COUNT): k_retry_after's counters
     void* topk = nullptr;                   // rl_top_keys scratch (topk_scratch_bytes), on first use
+    void* usage = nullptr;                  // rl_limiter_usage / rl_top_consumers scratch, on first use
+    uint32_t usage_passes = 0;              // table passes of the last rl_top_consumers (rl_debug_fetch)
 };
 
 #define HIP_OK(x)                                                      \
@@ -354,7 +356,7 @@ extern "C" void rl_destroy(rl_engine* e) {
     dfree(e->walk_tab);
     dfree(e->route_list); dfree(e->route_start); dfree(e->route_cnt);
     dfree(e->order); dfree(e->order_meta); dfree(e->solo_list);
-    dfree(e->d_stats); dfree(e->retry_dbg); dfree(e->topk);
+    dfree(e->d_stats); dfree(e->retry_dbg); dfree(e->topk); dfree(e->usage);
     dfree(e->s_key); dfree(e->s_permits); dfree(e->s_now); dfree(e->s_lim); dfree(e->s_op);
     dfree(e->s_allowed); dfree(e->s_remaining); dfree(e->s_tokens);
     dfree(e->route_scratch); dfree(e->route_counts); dfree(e->d_dir);
@@ -1310,6 +1312,141 @@ extern "C" int rl_top_keys(rl_engine* e, size_t n, const uint64_t* key_hash, uin
     return RL_OK;
 }
 
+// ---------------------------------------------------------------- census of a limiter's table
+// rl_usage.hip on the engine stream, behind every batch submitted before (as rl_export_state:
+// the decision stage and the unpermute run on or are joined on e->stream, with RL_OPT_PIPELINE
+// too). Both calls read the table as installed (no collect_status: a growth the last batch asked
+// for is not applied, its status stays uncollected) and touch no limiter state, batch scratch,
+// d_stats, d_ctl or status word.
+static_assert(RL_USAGE_BINS == kUsageBins, "histogram bins");
+static_assert(RL_USAGE_CANDIDATES == kUsageCandidates, "candidate cap");
+static_assert(sizeof(rl_usage) == 8 * (7 + RL_USAGE_BINS), "rl_usage layout");
+
+static int usage_scratch(rl_engine* e, UsageScratch* sc) {
+    if (!e->usage) {
+        int rc = dalloc(&e->usage, usage_scratch_bytes());
+        if (rc != RL_OK) return rc;
+    }
+    *sc = usage_scratch_at(e->usage);
+    return RL_OK;
+}
+
+extern "C" int rl_limiter_usage(rl_engine* e, uint16_t limiter, int64_t now_ns, rl_usage* out) {
+    if (!e || !out) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (limiter >= e->lims.size()) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    UsageScratch sc;
+    int rc = usage_scratch(e, &sc);
+    if (rc != RL_OK) return rc;
+    const HostLimiter& h = e->lims[limiter];
+    const uint64_t n_slots = h.table_bytes / sizeof(Slot);
+    hipStream_t s = e->stream;
+    unsigned long long c[kUcWords];
+    HIP_OK(hipMemsetAsync(sc.counters, 0, 32 * sizeof(unsigned long long), s));
+    HIP_OK(launch_usage_census(sc, (const Slot*)h.table, n_slots, h.dev, floor_div_ms(now_ns), s));
+    HIP_OK(hipMemcpyAsync(c, sc.counters, sizeof(c), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    out->slots = n_slots;
+    out->used_slots = c[kUcUsedSlots];
+    out->live_keys = c[kUcLive];
+    out->redis_keys = c[kUcRedis];
+    out->exhausted_keys = c[kUcExhausted];
+    out->cache_blocked = c[kUcCacheBlocked];
+    out->used_permits = c[kUcUsedPermits];
+    for (uint32_t b = 0; b < kUsageBins; ++b) out->hist[b] = c[kUcHist + b];
+    return RL_OK;
+}
+
+// MSD radix select over C = used << 64 | ~key_hash (largest first = used descending, key_hash
+// ascending): every pass histograms the next 12-bit digit of the keys that match the prefix
+// chosen so far, the host picks the digit in which the k-th key lies, and refinement stops as
+// soon as that cut bin holds at most RL_USAGE_CANDIDATES keys (or no bit is left: one key).
+// The compaction then fetches the cut bin and the fewer than k keys above it, ordered here.
+extern "C" int rl_top_consumers(rl_engine* e, uint16_t limiter, int64_t now_ns, uint32_t k,
+                                int64_t min_used, uint64_t* key_hash, int64_t* used, size_t* n_out,
+                                uint64_t* n_match) {
+    if (!e || !key_hash || !used || !n_out || !n_match || k == 0 || k > RL_TOP_KEYS_MAX || min_used < 0)
+        return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (limiter >= e->lims.size()) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    UsageScratch sc;
+    int rc = usage_scratch(e, &sc);
+    if (rc != RL_OK) return rc;
+    const HostLimiter& h = e->lims[limiter];
+    const uint64_t n_slots = h.table_bytes / sizeof(Slot);
+    const int64_t now = floor_div_ms(now_ns);
+    hipStream_t s = e->stream;
+    uint32_t ubits = 0;                              // bit_length(max_permits): used <= max_permits
+    while (ubits < 63 && ((uint64_t)h.dev.max_permits >> ubits) != 0) ++ubits;
+    UsageSel sel{};
+    sel.min_used = min_used;
+    sel.top = ubits + 64;
+    unsigned __int128 prefix = 0;
+    std::vector<unsigned long long> hist(kUsageDigits);
+    uint64_t matched = 0, need = 0, keep = 0, cut_count = 0;
+    e->usage_passes = 0;
+    for (bool first = true;; first = false) {
+        const uint32_t width = std::min<uint32_t>(kUsageDigitBits, sel.top);
+        sel.pos = sel.top - width;
+        sel.prefix_hi = (uint64_t)(prefix >> 64);
+        sel.prefix_lo = (uint64_t)prefix;
+        HIP_OK(hipMemsetAsync(sc.hist, 0, kUsageDigits * sizeof(unsigned long long), s));
+        HIP_OK(launch_usage_digits(sc, (const Slot*)h.table, n_slots, h.dev, now, sel, s));
+        HIP_OK(hipMemcpyAsync(hist.data(), sc.hist, kUsageDigits * sizeof(unsigned long long),
+                              hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+        e->usage_passes += 1;
+        if (first) {
+            for (uint32_t b = 0; b < (1u << width); ++b) matched += hist[b];
+            if (matched == 0) {
+                *n_out = 0;
+                *n_match = 0;
+                return RL_OK;
+            }
+            keep = need = std::min<uint64_t>(k, matched);
+        }
+        // the digit that holds the need-th largest of the keys under the prefix
+        uint64_t above = 0;
+        uint32_t cut = (1u << width) - 1;
+        for (;; --cut) {
+            if (above + hist[cut] >= need) break;
+            above += hist[cut];
+            if (cut == 0) return RL_E_INTERNAL;      // (the bins sum to the previous cut bin >= need)
+        }
+        need -= above;
+        cut_count = hist[cut];
+        prefix = (prefix << width) | cut;
+        sel.top = sel.pos;
+        if (cut_count <= kUsageCandidates || sel.top == 0) break;
+    }
+    sel.prefix_hi = (uint64_t)(prefix >> 64);
+    sel.prefix_lo = (uint64_t)prefix;
+    const uint64_t expect = (keep - need) + cut_count;   // the keys above the cut bin, and the bin
+    if (expect > kUsageStore) return RL_E_INTERNAL;
+    unsigned long long got = 0;
+    HIP_OK(hipMemsetAsync(sc.counters + kUsageCandCount, 0, sizeof(unsigned long long), s));
+    HIP_OK(launch_usage_compact(sc, (const Slot*)h.table, n_slots, h.dev, now, sel, s));
+    HIP_OK(hipMemcpyAsync(&got, sc.counters + kUsageCandCount, sizeof(got), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    e->usage_passes += 1;
+    if (got != expect) return RL_E_INTERNAL;
+    std::vector<UsageCand> cand(got);
+    HIP_OK(hipMemcpy(cand.data(), sc.cand, got * sizeof(UsageCand), hipMemcpyDeviceToHost));
+    std::partial_sort(cand.begin(), cand.begin() + (long)keep, cand.end(),
+                      [](const UsageCand& x, const UsageCand& y) {
+                          return x.used != y.used ? x.used > y.used : x.key_hash < y.key_hash;
+                      });
+    for (uint64_t i = 0; i < keep; ++i) {
+        key_hash[i] = cand[i].key_hash;
+        used[i] = cand[i].used;
+    }
+    *n_out = (size_t)keep;
+    *n_match = matched;
+    return RL_OK;
+}
+
 extern "C" int rl_batch_stats_get(rl_engine* e, rl_batch_stats* out) {
     if (!e || !out) return RL_E_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
@@ -1755,6 +1892,11 @@ extern "C" int rl_debug_fetch(rl_engine* e, const char* what, void* out, size_t 
         const size_t nb = std::min(bytes, ((size_t)1 << kMaxDigitBits) * sizeof(uint32_t));
         HIP_OK(hipMemcpy(out, B.bin_total, nb, hipMemcpyDeviceToHost));
         return (int)(nb / sizeof(uint32_t));
+    }
+    if (std::strcmp(what, "usage_passes") == 0) {    // table passes of the last rl_top_consumers
+        if (bytes < sizeof(uint32_t)) return RL_E_INVALID_ARG;
+        std::memcpy(out, &e->usage_passes, sizeof(uint32_t));
+        return 1;
     }
 #ifdef RL_RETRY_COUNT
     if (std::strcmp(what, "retry_counts") == 0) {    // {searches, bisections, buckets probed}

@@ -466,6 +466,42 @@ hipError_t launch_topk_pass(const TopkScratch& sc, int pass, const uint64_t* key
 // compact + select: writes top_key / top_count [0, n_out) and hdr = {n_out, n_heavy, overflow, n}
 hipError_t launch_topk_select(const TopkScratch& sc, uint32_t k, uint64_t min_count, uint64_t n,
                               uint64_t* top_key, uint64_t* top_count, uint64_t* hdr, hipStream_t s);
+// Census of one limiter's table (rl_usage.hip): every kernel is one read-only pass over the
+// limiter's slots (and cache words) that evaluates each slot with the peek code at `now`.
+// One scratch of fixed size (usage_scratch_bytes) holds the counters, the digit histogram of
+// the radix select and the candidate store.
+constexpr uint32_t kUsageBins = 16;               // RL_USAGE_BINS
+constexpr uint32_t kUsageCandidates = 65536;      // RL_USAGE_CANDIDATES: largest cut bin compacted
+constexpr uint32_t kUsageDigitBits = 12;          // the select's digit
+constexpr uint32_t kUsageDigits = 1u << kUsageDigitBits;
+constexpr uint32_t kUsageStore = kUsageCandidates + kTopkMax;   // the cut bin + the < k keys above it
+// the counters of k_usage_census, in this order (then hist[kUsageBins])
+enum : uint32_t { kUcUsedSlots = 0, kUcLive, kUcRedis, kUcExhausted, kUcCacheBlocked, kUcUsedPermits,
+                  kUcHist, kUcWords = kUcHist + kUsageBins };
+struct UsageCand { uint64_t key_hash; int64_t used; };
+struct UsageScratch {
+    unsigned long long* counters;  // [32]: kUcWords census counters; [31] = candidates appended
+    unsigned long long* hist;      // [kUsageDigits]
+    UsageCand* cand;               // [kUsageStore]
+};
+constexpr uint32_t kUsageCandCount = 31;
+size_t usage_scratch_bytes();
+UsageScratch usage_scratch_at(void* base);
+// The select ranks live keys with used >= min_used by the composite C = used << 64 | ~key_hash
+// (a 128-bit value of `bits` significant bits), largest first. A pass looks at the keys with
+// C >> top == prefix and counts their digit (C >> pos) & (2^(top - pos) - 1); the compaction
+// appends every key with C >> top >= prefix.
+struct UsageSel {
+    int64_t min_used;
+    uint64_t prefix_hi, prefix_lo;
+    uint32_t top, pos;
+};
+hipError_t launch_usage_census(const UsageScratch& sc, const Slot* table, uint64_t n_slots,
+                               const DevLimiter& L, int64_t now_ms, hipStream_t s);
+hipError_t launch_usage_digits(const UsageScratch& sc, const Slot* table, uint64_t n_slots,
+                               const DevLimiter& L, int64_t now_ms, const UsageSel& sel, hipStream_t s);
+hipError_t launch_usage_compact(const UsageScratch& sc, const Slot* table, uint64_t n_slots,
+                                const DevLimiter& L, int64_t now_ms, const UsageSel& sel, hipStream_t s);
 hipError_t launch_owner_partition(const uint64_t* key, uint32_t n, uint32_t shard_count,
                                   uint32_t* perm, uint32_t* counts_dev, uint32_t* scratch,
                                   const DirSlot* dir, hipStream_t s);

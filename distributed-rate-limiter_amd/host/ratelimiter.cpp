@@ -90,6 +90,40 @@ std::vector<std::pair<uint64_t, uint64_t>> GpuEngine::topKeys(const uint64_t* ha
     return out;
 }
 
+rl_usage GpuEngine::usage(uint16_t limiter, int64_t nowNanos) {
+    rl_usage u{};
+    int st;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        st = rl_limiter_usage(e_, limiter, nowNanos, &u);
+    }
+    if (st == RL_E_INVALID_ARG) throw IllegalArgumentException(std::string("usage: ") + rl_strerror(st));
+    if (st != RL_OK) throw StorageException(std::string("usage: ") + rl_strerror(st), st);
+    return u;
+}
+
+std::vector<std::pair<uint64_t, int64_t>> GpuEngine::topConsumers(uint16_t limiter, int64_t nowNanos,
+                                                                  uint32_t k, int64_t minUsed,
+                                                                  uint64_t* nMatch) {
+    if (k == 0 || k > RL_TOP_KEYS_MAX || minUsed < 0)
+        throw IllegalArgumentException("topConsumers: k in [1, RL_TOP_KEYS_MAX], minUsed >= 0");
+    std::vector<uint64_t> key(k);
+    std::vector<int64_t> used(k);
+    size_t nOut = 0;
+    uint64_t matched = 0;
+    int st;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        st = rl_top_consumers(e_, limiter, nowNanos, k, minUsed, key.data(), used.data(), &nOut, &matched);
+    }
+    if (st == RL_E_INVALID_ARG) throw IllegalArgumentException(std::string("topConsumers: ") + rl_strerror(st));
+    if (st != RL_OK) throw StorageException(std::string("topConsumers: ") + rl_strerror(st), st);
+    if (nMatch) *nMatch = matched;
+    std::vector<std::pair<uint64_t, int64_t>> out(nOut);
+    for (size_t i = 0; i < nOut; ++i) out[i] = {key[i], used[i]};
+    return out;
+}
+
 GpuRateLimiter::GpuRateLimiter(std::shared_ptr<GpuEngine> engine, Algorithm algo,
                                const RateLimitConfig& cfg, Clock clock, int batchWindowMicros)
     : allowedRequests(algo == Algorithm::TokenBucket ? "ratelimiter.tokenbucket.allowed"
@@ -241,6 +275,36 @@ int64_t GpuRateLimiter::retryAfterMillis(const std::string& key, int permits) {
     if (st == RL_E_INVALID_REQUEST || wait == RL_RETRY_INVALID)
         throw IllegalArgumentException("retryAfterMillis: invalid request");
     return wait;                                     // RL_RETRY_NEVER = -1: never
+}
+
+// The census calls run like retryAfterMillis: behind every tryAcquire that has returned, holding
+// the flush slot, with the clock read under mu_.
+rl_usage GpuRateLimiter::usage() {
+    std::unique_lock<std::mutex> lk(mu_);
+    cv_.wait(lk, [&] { return !flushing_; });
+    flushing_ = true;
+    const int64_t now = clock_();
+    lk.unlock();
+    struct Release {
+        GpuRateLimiter* self; std::unique_lock<std::mutex>& lk;
+        ~Release() { lk.lock(); self->flushing_ = false; self->cv_.notify_all(); }
+    } rel{this, lk};
+    return engine_->usage(id_, now);
+}
+
+std::vector<std::pair<uint64_t, int64_t>> GpuRateLimiter::topConsumers(uint32_t k, int64_t minUsed) {
+    if (k == 0 || k > RL_TOP_KEYS_MAX || minUsed < 0)
+        throw IllegalArgumentException("topConsumers: k in [1, RL_TOP_KEYS_MAX], minUsed >= 0");
+    std::unique_lock<std::mutex> lk(mu_);
+    cv_.wait(lk, [&] { return !flushing_; });
+    flushing_ = true;
+    const int64_t now = clock_();
+    lk.unlock();
+    struct Release {
+        GpuRateLimiter* self; std::unique_lock<std::mutex>& lk;
+        ~Release() { lk.lock(); self->flushing_ = false; self->cv_.notify_all(); }
+    } rel{this, lk};
+    return engine_->topConsumers(id_, now, k, minUsed);
 }
 
 void GpuRateLimiter::tryAcquireBatch(size_t n, const uint64_t* keyHash, const int32_t* permits,

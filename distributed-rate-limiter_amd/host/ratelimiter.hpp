@@ -130,6 +130,14 @@ class GpuEngine {
     // (RL_E_CAPACITY), IllegalArgumentException for k == 0, k > RL_TOP_KEYS_MAX, minCount == 0.
     std::vector<std::pair<uint64_t, uint64_t>> topKeys(const uint64_t* hashes, size_t n, uint32_t k,
                                                        uint64_t minCount);
+    // rl_limiter_usage: census of a limiter's table at nowNanos (read-only).
+    rl_usage usage(uint16_t limiter, int64_t nowNanos);
+    // rl_top_consumers: the (key hash, used permits) pairs of the at most k live keys of the
+    // limiter that have used at least minUsed permits at nowNanos, used descending then hash
+    // ascending; exact however many keys tie. nMatch (nullable) = how many keys qualify.
+    // IllegalArgumentException for k == 0, k > RL_TOP_KEYS_MAX, minUsed < 0.
+    std::vector<std::pair<uint64_t, int64_t>> topConsumers(uint16_t limiter, int64_t nowNanos, uint32_t k,
+                                                           int64_t minUsed, uint64_t* nMatch = nullptr);
 
   private:
     rl_engine* e_ = nullptr;
@@ -164,6 +172,14 @@ class GpuRateLimiter : public RateLimiter {
     // DemoController.rateLimitExceeded). Not part of the reference's RateLimiter interface.
     // Read-only; it sees every tryAcquire of this object that has returned.
     int64_t retryAfterMillis(const std::string& key, int permits = 1);
+    // What is in this limiter's table at the clock's now (DBSIZE / INFO keyspace of the
+    // reference's Redis; the numbers behind /api/health): slots, live and throttled keys, permits
+    // in use. Read-only; sees every tryAcquire of this object that has returned.
+    rl_usage usage();
+    // The at most k live keys that have used at least minUsed permits, heaviest first, as
+    // (keyHash(key), used) pairs (the candidates for reset(key) or an abuse report). Exact.
+    // Throws IllegalArgumentException for k == 0, k > RL_TOP_KEYS_MAX, minUsed < 0.
+    std::vector<std::pair<uint64_t, int64_t>> topConsumers(uint32_t k, int64_t minUsed = 1);
     // the reference's permits check (SlidingWindowRateLimiter.java:87-89,
     // TokenBucketRateLimiter.java:106-108): throws IllegalArgumentException for permits <= 0
     static void requirePositive(int permits);

@@ -32,6 +32,7 @@ OP_ACQUIRE, OP_PEEK, OP_RESET = 0, 1, 2
 REM_UNKNOWN, REM_INVALID, REM_ERROR = -1, -2, -3
 RETRY_NEVER, RETRY_INVALID = -1, -2   # RL_RETRY_* (rl_retry_after)
 TOP_KEYS_MAX, TOP_KEYS_CANDIDATES = 4096, 65536   # RL_TOP_KEYS_* (rl_top_keys)
+USAGE_BINS, USAGE_CANDIDATES = 16, 65536   # RL_USAGE_* (rl_limiter_usage, rl_top_consumers)
 OPT_STAGE_TIMING = 1
 OPT_PIPELINE = 2       # RL_OPT_PIPELINE: partition of batch k+1 overlaps batch k's decisions
 OPT_FIXED_CAPACITY = 4  # RL_OPT_FIXED_CAPACITY: no on-demand table growth
@@ -54,6 +55,7 @@ EXPORTS = [
     "rl_grow_limiter", "rl_limiter_slots", "rl_router_create_ex", "rl_router_stats_get",
     "rl_retry_after", "rl_retry_after_device",
     "rl_top_keys", "rl_top_keys_device", "rl_router_plan_directory_sampled",
+    "rl_limiter_usage", "rl_top_consumers",
 ]
 RCCL_EXPORTS = ["rl_rccl_unique_id", "rl_transport_rccl_create", "rl_transport_rccl_destroy"]
 STATE_SW_BUCKET, STATE_TB_BUCKET = 0, 1
@@ -92,6 +94,14 @@ class BatchStats(ctypes.Structure):
                                                  "capacity_errors", "regions_touched",
                                                  "table_bytes", "cache_hits", "table_grows",
                                                  "hot_regions", "routed")]
+
+
+class Usage(ctypes.Structure):
+    """rl_usage (include/rl_engine.h): census of one limiter's table at one instant."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("slots", "used_slots", "live_keys", "redis_keys",
+                                                 "exhausted_keys", "cache_blocked",
+                                                 "used_permits")] + \
+               [("hist", ctypes.c_uint64 * USAGE_BINS)]
 
 
 class TraceSpec(ctypes.Structure):
@@ -182,6 +192,9 @@ def lib():
     L.rl_top_keys_device.argtypes = [vp, sz, vp, u32, ctypes.c_uint64, vp, vp, vp, vp]
     L.rl_router_plan_directory_sampled.argtypes = [vp, sz, vp, u32, ctypes.c_uint64,
                                                    ctypes.POINTER(u32), vp]
+    L.rl_limiter_usage.argtypes = [vp, u16, i64, ctypes.POINTER(Usage)]
+    L.rl_top_consumers.argtypes = [vp, u16, i64, u32, i64, vp, vp, ctypes.POINTER(sz),
+                                   ctypes.POINTER(ctypes.c_uint64)]
     L.rl_owner_of_engine.restype = u32
     _lib = L
     return L
@@ -418,6 +431,33 @@ class Engine:
         if overflow:
             raise RlError(RL_E_CAPACITY, "rl_top_keys_device")
         return top[:n_out].view(torch.uint64), cnt[:n_out].view(torch.uint64), n_heavy
+
+    def limiter_usage(self, limiter, now_ns) -> dict:
+        """Census of one limiter's table at now_ns (rl_limiter_usage): a dict of the rl_usage
+        fields, `hist` as a list of USAGE_BINS counts. Read-only."""
+        u = Usage()
+        st = self._L.rl_limiter_usage(self._h, int(limiter), int(now_ns), ctypes.byref(u))
+        if st != RL_OK:
+            raise RlError(st, "rl_limiter_usage")
+        d = {f: getattr(u, f) for f, _ in Usage._fields_ if f != "hist"}
+        d["hist"] = list(u.hist)
+        return d
+
+    def top_consumers(self, limiter, now_ns, k, min_used=1):
+        """The live keys of a limiter that have used at least min_used permits at now_ns, the k
+        heaviest first (used descending, key hash ascending), exact however many tie
+        (rl_top_consumers). Returns (key hashes uint64, used int64, n_match). Read-only."""
+        k = int(k)
+        keys = np.zeros(max(min(k, TOP_KEYS_MAX), 0), np.uint64)
+        used = np.zeros(keys.shape[0], np.int64)
+        n_out = ctypes.c_size_t(0)
+        n_match = ctypes.c_uint64(0)
+        st = self._L.rl_top_consumers(self._h, int(limiter), int(now_ns), k, int(min_used),
+                                      _p(keys), _p(used), ctypes.byref(n_out),
+                                      ctypes.byref(n_match))
+        if st != RL_OK:
+            raise RlError(st, "rl_top_consumers")
+        return keys[:n_out.value], used[:n_out.value], n_match.value
 
     def export_state(self, now_ns):
         """Live state at now_ns in the Redis layout: a STATE_DTYPE array (rl_export_state)."""

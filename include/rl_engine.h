@@ -309,7 +309,8 @@ int  rl_tune(rl_engine* e, const char* key, int64_t value);
 /* Diagnostics (not needed by callers). "region_times": after a batch run with
  * rl_tune("debug_regions", 1), copies per-bin {t_start, t_end, records, rounds, cycle
  * counters} (uint64 x28 per bin; s_memrealtime ticks; rounds bit 63 = a hot region).
- * Returns the number of bins copied (>= 0) or a status < 0. */
+ * Returns the number of bins copied (>= 0) or a status < 0. "usage_passes": one uint32, the
+ * table passes of the last rl_top_consumers call (digit passes + the compaction); returns 1. */
 int  rl_debug_fetch(rl_engine* e, const char* what, void* out, size_t bytes);
 const char* rl_strerror(int status);
 int  rl_abi_version(void);
@@ -360,6 +361,59 @@ int  rl_import_state(rl_engine* e, const rl_state_entry* in, size_t n, size_t* n
  * drop dead slots of the regions they load.) now_ns must not exceed the now of any later request,
  * as with Redis's own clock. *reclaimed (nullable) = slots freed. */
 int  rl_sweep_expired(rl_engine* e, int64_t now_ns, uint64_t* reclaimed);
+
+/* ---- census of a limiter's table --------------------------------------------------
+ * What DBSIZE / INFO keyspace / SCAN answer for the reference's Redis, computed on the device in
+ * table passes that return a few hundred bytes (rl_export_state moves 56 B per Redis key and
+ * sorts on the host). For limiter L and now = floorDiv(now_ns, 1e6):
+ *   live key        a key with at least one Redis key live at now, the rule rl_export_state
+ *                   applies (SW: a bucket with !(now > last INCR + w); TB: !(now > last_refill + 2w))
+ *   available(key)  what RL_OP_PEEK returns for the key at now (SW: max(0, max - estimate); TB:
+ *                   the (long) of the refilled balance, negative after time regression), from
+ *                   the engine's own decision code, so exact
+ *   used(key)       max_permits - clamp(available, 0, max_permits), in [0, max_permits]
+ * Both calls only read: no limiter state, cache word, batch statistic, and not the status
+ * rl_last_status reports, which they do not collect either. They read the table as installed: a
+ * growth the last batch asked for but nobody has collected is not applied (as rl_export_state).
+ * They run on the engine's stream behind every batch submitted before them (RL_OPT_PIPELINE
+ * included) and synchronise. RL_E_INVALID_ARG, before any device call and with every output
+ * untouched: a null engine (checked first), an unknown limiter, a null output pointer, k == 0,
+ * k > RL_TOP_KEYS_MAX, min_used < 0. Their scratch (1,147,136 B = 1.09 MiB, whatever the
+ * table's size: 32 counters, a 4096-bin digit histogram, RL_USAGE_CANDIDATES + RL_TOP_KEYS_MAX
+ * 16-B candidates) is allocated by the first call and freed by rl_destroy. Multi-GPU: an engine
+ * reports its own shard; a key has one owner, so the ranks' rl_usage fields add up. */
+#define RL_USAGE_BINS 16
+typedef struct rl_usage {
+    uint64_t slots;          /* == rl_limiter_slots                                      */
+    uint64_t used_slots;     /* slots that are not free (live keys + tombstones)          */
+    uint64_t live_keys;
+    uint64_t redis_keys;     /* entries rl_export_state(now_ns) emits for this limiter   */
+    uint64_t exhausted_keys; /* live keys with used == max_permits (tryAcquire(key,1) denied
+                                on the Redis state)                                       */
+    uint64_t cache_blocked;  /* SW + RL_LIM_LOCAL_CACHE: keys whose cache entry rejects at now
+                                (cache word x != 0 && now < x); 0 otherwise              */
+    uint64_t used_permits;   /* sum of used(key) over live keys (modulo 2^64)             */
+    uint64_t hist[RL_USAGE_BINS]; /* live keys by bin = used == max ? 15 : used * 16 / max
+                                     (integer division); sums to live_keys                */
+} rl_usage;
+/* One pass over the limiter's slots (32 B each, + 8 B with a cache table). */
+int  rl_limiter_usage(rl_engine* e, uint16_t limiter, int64_t now_ns, rl_usage* out);
+/* The heaviest consumers: M = { live keys with used >= min_used }, ordered by used descending
+ * and then key_hash ascending as an unsigned 64-bit value;
+ *   n_match = |M| (exact),  n_out = min(k, n_match),
+ *   key_hash / used [0, n_out) = the first n_out elements of M;
+ * entries at and beyond n_out are left untouched. The answer is unique and always exact: there
+ * is no overflow or approximate mode, however many keys tie (every throttled key has used ==
+ * max_permits). Method: a most-significant-digit radix select over the composite (used in
+ * bit_length(max_permits) bits, then ~key_hash) in 12-bit digits, one table pass per digit,
+ * until the bin that holds the k-th key has at most RL_USAGE_CANDIDATES keys; one more pass then
+ * fetches that bin and the fewer than k keys above it, and the host orders them. With hashed
+ * keys that is 2 or 3 digit passes + 1 (each pass divides a tie by 4096); the worst case, for
+ * max_permits = 2^53 and adversarial key hashes, is ceil((54 + 64) / 12) + 1 = 11 passes. The
+ * host reads a 32-KB histogram between passes, hence no stream / device-buffer form. */
+#define RL_USAGE_CANDIDATES 65536
+int  rl_top_consumers(rl_engine* e, uint16_t limiter, int64_t now_ns, uint32_t k, int64_t min_used,
+                      uint64_t* key_hash, int64_t* used, size_t* n_out, uint64_t* n_match);
 
 /* ---- multi-GPU routing helpers (device buffers, engine stream) ------------
  * owner(key_hash) is the shard that holds the key's state. rl_route_partition
