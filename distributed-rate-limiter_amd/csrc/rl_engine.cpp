@@ -1622,7 +1622,9 @@ extern "C" int rl_route_partition(rl_engine* e, size_t n, const uint64_t* key_ha
 
 // Hot-key owner directory: key_hash[i] is owned by owner[i] instead of its hash owner.
 // Every rank of a router must install the same directory, before any state exists for
-// those keys (or after moving it with rl_export_state / rl_import_state).
+// those keys. That holds for this call and rl_router_plan_directory only:
+// rl_router_replan_directory moves the state of the keys that change owner (rl_copy_keys /
+// rl_put_keys / rl_drop_keys below) and then installs the directory through this call.
 extern "C" int rl_set_owner_directory(rl_engine* e, size_t n, const uint64_t* key_hash,
                                       const uint32_t* owner) {
     if (!e || (n && (!key_hash || !owner)) || n > kDirMax) return RL_E_INVALID_ARG;
@@ -1724,6 +1726,19 @@ int route_pack_wire_mm(rl_engine* e, size_t n, const uint32_t* perm, const uint6
 }
 int engine_device(rl_engine* e) { return e ? e->device : 0; }
 size_t engine_max_batch(rl_engine* e) { return e ? (size_t)e->opts.max_batch : 0; }
+size_t engine_limiters(rl_engine* e) {
+    if (!e) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return e->lims.size();
+}
+size_t engine_directory(rl_engine* e, uint64_t* keys, uint32_t* owners) {
+    if (!e || !keys || !owners) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    size_t n = 0;
+    for (const DirSlot& d : e->h_dir)
+        if (d.owner != kDirEmpty && n < kDirMax) { keys[n] = unmix64(d.tag); owners[n++] = d.owner; }
+    return n;
+}
 }  // namespace rl
 
 extern "C" int rl_route_unwire(rl_engine* e, size_t m, const uint64_t* wire, uint32_t n_src,
@@ -1962,6 +1977,81 @@ extern "C" int rl_export_state(rl_engine* e, int64_t now_ns, rl_state_entry* out
     return rc;
 }
 
+// A slot image bound for the region at `addr` (its local-cache words at `xaddr`, 0: none), and
+// the rebuild of every region that receives some (k_import), shared by rl_import_state and
+// rl_put_keys: images in `imgs` order per region, `with_x` = carry their cache words (the state
+// import writes 0). *fail = images that found no free slot. Synchronises the engine stream.
+namespace {
+struct RegionImg { uint64_t addr, xaddr; uint8_t algo; Slot s; uint64_t x; };
+
+RegionImg region_img(const rl_engine* e, const HostLimiter& h, uint64_t tag) {
+    RegionImg im{};
+    const uint32_t region = region_local(tag, e->shard_bits, h.dev.region_bits);
+    im.algo = (uint8_t)h.dev.algo;
+    im.s.tag = tag;
+    im.addr = (uint64_t)(uintptr_t)h.table + (uint64_t)region * kRegionSlots * sizeof(Slot);
+    im.xaddr = h.cache_table ? (uint64_t)(uintptr_t)h.cache_table +
+                                   (uint64_t)region * kRegionSlots * sizeof(uint64_t) : 0;
+    return im;
+}
+
+int apply_region_images(rl_engine* e, std::vector<RegionImg>& imgs, bool with_x, uint32_t* fail_out) {
+    *fail_out = 0;
+    if (imgs.empty()) return RL_OK;
+    std::stable_sort(imgs.begin(), imgs.end(),
+                     [](const RegionImg& x, const RegionImg& y) { return x.addr < y.addr; });
+    std::vector<uint32_t> off;
+    std::vector<uint64_t> addr, xaddr, xw(imgs.size());
+    std::vector<uint8_t> algo;
+    std::vector<Slot> slots(imgs.size());
+    for (size_t k = 0; k < imgs.size(); ++k) {
+        if (k == 0 || imgs[k].addr != imgs[k - 1].addr) {
+            off.push_back((uint32_t)k);
+            addr.push_back(imgs[k].addr);
+            xaddr.push_back(imgs[k].xaddr);
+            algo.push_back(imgs[k].algo);
+        }
+        slots[k] = imgs[k].s;
+        xw[k] = imgs[k].x;
+    }
+    off.push_back((uint32_t)imgs.size());
+    const size_t G = addr.size(), N = slots.size();
+    const size_t bytes = N * sizeof(Slot) + N * 8 + G * 16 + (G + 1) * 4 + G + 16;
+    uint8_t* d = nullptr;
+    if (dalloc(&d, bytes) != RL_OK) return RL_E_NOMEM;
+    Slot* d_img = (Slot*)d;
+    uint64_t* d_xw = (uint64_t*)(d + N * sizeof(Slot));
+    uint64_t* d_addr = d_xw + N;
+    uint64_t* d_xaddr = d_addr + G;
+    uint32_t* d_off = (uint32_t*)(d_xaddr + G);
+    uint32_t* d_fail = d_off + G + 1;
+    uint8_t* d_algo = (uint8_t*)(d_fail + 1);
+    int rc = RL_OK;
+    uint32_t fail = 0;
+    if (hipMemcpyAsync(d_img, slots.data(), N * sizeof(Slot), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
+        (with_x && hipMemcpyAsync(d_xw, xw.data(), N * 8, hipMemcpyHostToDevice, e->stream) != hipSuccess) ||
+        hipMemcpyAsync(d_addr, addr.data(), G * 8, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
+        hipMemcpyAsync(d_xaddr, xaddr.data(), G * 8, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
+        hipMemcpyAsync(d_off, off.data(), (G + 1) * 4, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
+        hipMemcpyAsync(d_algo, algo.data(), G, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
+        hipMemsetAsync(d_fail, 0, 4, e->stream) != hipSuccess)
+        rc = RL_E_DEVICE;
+    if (rc == RL_OK) {
+        ImportArgs a{};
+        a.n_groups = (uint32_t)G; a.group_off = d_off; a.region_addr = d_addr; a.xregion_addr = d_xaddr;
+        a.group_algo = d_algo;
+        a.img = d_img; a.xw = with_x ? d_xw : nullptr; a.fail = d_fail;
+        if (launch_import(a, e->stream) != hipSuccess ||
+            hipMemcpyAsync(&fail, d_fail, 4, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+            hipStreamSynchronize(e->stream) != hipSuccess)
+            rc = RL_E_DEVICE;
+    }
+    (void)hipFree(d);
+    *fail_out = fail;
+    return rc;
+}
+}  // namespace
+
 extern "C" int rl_import_state(rl_engine* e, const rl_state_entry* in, size_t n, size_t* n_imported) {
     if (!e || (n && !in)) return RL_E_INVALID_ARG;
     if (n_imported) *n_imported = 0;
@@ -1990,8 +2080,7 @@ extern "C" int rl_import_state(rl_engine* e, const rl_state_entry* in, size_t n,
         if (x->key_hash != y->key_hash) return x->key_hash < y->key_hash;
         return x->window_start_ms > y->window_start_ms;
     });
-    struct Img { uint64_t addr, xaddr; uint8_t algo; Slot s; };
-    std::vector<Img> imgs;
+    std::vector<RegionImg> imgs;
     size_t taken = 0;
     for (size_t i = 0; i < n;) {
         size_t j = i + 1;
@@ -2003,10 +2092,8 @@ extern "C" int rl_import_state(rl_engine* e, const rl_state_entry* in, size_t n,
         const bool mine = e->opts.shard_count <= 1 ||
                           (uint32_t)(tag >> (64 - e->shard_bits)) == e->opts.shard_index;
         if (mine) {
-            Img im{};
-            im.algo = (uint8_t)L.algo;
-            im.s.tag = tag;
-            if (L.algo == kAlgoTB) {                   // one hash per key: the first one wins
+            RegionImg im = region_img(e, h, tag);
+            if (L.algo == kAlgoTB) {                  // one hash per key: the first one wins
                 uint64_t bits;
                 std::memcpy(&bits, &x.tokens, 8);
                 im.s.a = bits; im.s.b = (uint64_t)x.last_refill_ms; im.s.c = 1;
@@ -2026,62 +2113,126 @@ extern "C" int rl_import_state(rl_engine* e, const rl_state_entry* in, size_t n,
                 im.s.b = c1 | (c0 << 32);
                 im.s.c = (uint64_t)(uint32_t)o1 | ((uint64_t)(uint32_t)o0 << 32);
             }
-            const uint32_t region = region_local(tag, e->shard_bits, L.region_bits);
-            im.addr = (uint64_t)(uintptr_t)h.table + (uint64_t)region * kRegionSlots * sizeof(Slot);
-            im.xaddr = h.cache_table ? (uint64_t)(uintptr_t)h.cache_table +
-                                           (uint64_t)region * kRegionSlots * sizeof(uint64_t) : 0;
             imgs.push_back(im);
         }
         i = j;
     }
     if (imgs.empty()) return RL_OK;
-    std::stable_sort(imgs.begin(), imgs.end(), [](const Img& x, const Img& y) { return x.addr < y.addr; });
-    std::vector<uint32_t> off;
-    std::vector<uint64_t> addr, xaddr;
-    std::vector<uint8_t> algo;
-    std::vector<Slot> slots(imgs.size());
-    for (size_t k = 0; k < imgs.size(); ++k) {
-        if (k == 0 || imgs[k].addr != imgs[k - 1].addr) {
-            off.push_back((uint32_t)k);
-            addr.push_back(imgs[k].addr);
-            xaddr.push_back(imgs[k].xaddr);
-            algo.push_back(imgs[k].algo);
-        }
-        slots[k] = imgs[k].s;
-    }
-    off.push_back((uint32_t)imgs.size());
-    const size_t G = addr.size();
-    const size_t bytes = slots.size() * sizeof(Slot) + G * 16 + (G + 1) * 4 + G + 16;
-    uint8_t* d = nullptr;
-    if (dalloc(&d, bytes) != RL_OK) return RL_E_NOMEM;
-    Slot* d_img = (Slot*)d;
-    uint64_t* d_addr = (uint64_t*)(d + slots.size() * sizeof(Slot));
-    uint64_t* d_xaddr = d_addr + G;
-    uint32_t* d_off = (uint32_t*)(d_xaddr + G);
-    uint32_t* d_fail = d_off + G + 1;
-    uint8_t* d_algo = (uint8_t*)(d_fail + 1);
-    int rc = RL_OK;
     uint32_t fail = 0;
-    if (hipMemcpyAsync(d_img, slots.data(), slots.size() * sizeof(Slot), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-        hipMemcpyAsync(d_addr, addr.data(), G * 8, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-        hipMemcpyAsync(d_xaddr, xaddr.data(), G * 8, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-        hipMemcpyAsync(d_off, off.data(), (G + 1) * 4, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-        hipMemcpyAsync(d_algo, algo.data(), G, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-        hipMemsetAsync(d_fail, 0, 4, e->stream) != hipSuccess)
-        rc = RL_E_DEVICE;
-    if (rc == RL_OK) {
-        ImportArgs a{};
-        a.n_groups = (uint32_t)G; a.group_off = d_off; a.region_addr = d_addr; a.xregion_addr = d_xaddr;
-        a.group_algo = d_algo;
-        a.img = d_img; a.fail = d_fail;
-        if (launch_import(a, e->stream) != hipSuccess ||
-            hipMemcpyAsync(&fail, d_fail, 4, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-            hipStreamSynchronize(e->stream) != hipSuccess)
-            rc = RL_E_DEVICE;
-    }
-    (void)hipFree(d);
+    const int rc = apply_region_images(e, imgs, /*with_x=*/false, &fail);
     if (rc != RL_OK) return rc;
     if (n_imported) *n_imported = taken;
+    return fail ? RL_E_CAPACITY : RL_OK;
+}
+
+// ---------------------------------------------------------------- key migration
+// rl_copy_keys / rl_drop_keys / rl_put_keys (rl_migrate.hip, k_import). Like the census they run
+// on the engine stream behind every batch submitted before them (the decision stage and the
+// unpermute run on or are joined on e->stream, with RL_OPT_PIPELINE too), work on the table as
+// installed (no collect_status) and touch no batch scratch, d_stats, d_ctl or status word.
+// The slot and its cache word are a key's whole state between batches: the hot-region route
+// list holds region ids chosen from the previous batch's record counts, the hot, walk and solo
+// lists and the escape arrays are rebuilt from each batch's own records, and hot_hint /
+// walk_hint only size scratch. None of them names a key or caches a slot's contents, so a put or
+// a drop between two batches needs to invalidate nothing.
+static_assert(sizeof(KeyImage) == sizeof(rl_key_image) && sizeof(rl_key_image) == 48, "rl_key_image layout");
+static_assert(offsetof(KeyImage, limiter) == offsetof(rl_key_image, limiter), "rl_key_image layout");
+static_assert(RL_MOVE_KEYS_MAX == kMoveKeysMax && RL_MOVE_KEYS_MAX >= 2 * kDirMax, "old + new directory");
+
+// Copy (out / cap) or drop (out = nullptr) of the listed keys under every limiter; *count =
+// the hits. Drop: key_hash 0 in a launch of its own (rl_migrate.hip).
+static int move_keys(rl_engine* e, size_t n, const uint64_t* key_hash, bool drop, rl_key_image* out,
+                     size_t cap, uint32_t* count) {
+    *count = 0;
+    std::vector<uint64_t> keys(key_hash, key_hash + n);
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    const size_t nk = keys.size(), n_lim = e->lims.size();
+    if (nk == 0 || n_lim == 0) return RL_OK;
+    const uint32_t dcap = drop ? 0u : (uint32_t)std::min<size_t>(cap, nk * n_lim);
+    uint64_t* d_keys = nullptr;
+    KeyImage* d_out = nullptr;
+    uint32_t* d_count = nullptr;
+    int rc = dalloc(&d_keys, nk);
+    if (rc == RL_OK) rc = dalloc(&d_out, std::max<uint32_t>(dcap, 1u));
+    if (rc == RL_OK) rc = dalloc(&d_count, 1);
+    hipStream_t s = e->stream;
+    if (rc == RL_OK && (hipMemcpyAsync(d_keys, keys.data(), nk * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+                        hipMemsetAsync(d_count, 0, sizeof(uint32_t), s) != hipSuccess))
+        rc = RL_E_DEVICE;
+    if (rc == RL_OK) {
+        MoveArgs a{};
+        a.key = d_keys; a.lims = e->d_lims; a.out = d_out; a.count = d_count;
+        a.n_keys = (uint32_t)nk; a.n_lim = (uint32_t)n_lim; a.cap = dcap; a.shard_bits = e->shard_bits;
+        hipError_t he = hipSuccess;
+        if (drop && keys[0] == 0) {                      // (sorted: key 0 comes first)
+            MoveArgs z = a;
+            z.n_keys = 1;
+            a.key = d_keys + 1; a.n_keys = (uint32_t)nk - 1;
+            he = launch_move_keys(a, true, s);
+            if (he == hipSuccess) he = launch_move_keys(z, true, s);
+        } else {
+            he = launch_move_keys(a, drop, s);
+        }
+        if (he != hipSuccess ||
+            hipMemcpyAsync(count, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess)
+            rc = RL_E_DEVICE;
+    }
+    if (rc == RL_OK && !drop && *count && *count <= cap) {
+        if (*count > dcap) {
+            rc = RL_E_INTERNAL;                          // (more hits than pairs)
+        } else if (hipMemcpy(out, d_out, (size_t)*count * sizeof(KeyImage), hipMemcpyDeviceToHost) != hipSuccess) {
+            rc = RL_E_DEVICE;
+        } else {
+            std::sort(out, out + *count, [](const rl_key_image& x, const rl_key_image& y) {
+                return x.limiter != y.limiter ? x.limiter < y.limiter : x.key_hash < y.key_hash;
+            });
+        }
+    }
+    dfree(d_keys); dfree(d_out); dfree(d_count);
+    return rc;
+}
+
+extern "C" int rl_copy_keys(rl_engine* e, size_t n, const uint64_t* key_hash, rl_key_image* out,
+                            size_t cap, size_t* n_out) {
+    if (!e || n > RL_MOVE_KEYS_MAX || (n && !key_hash) || !n_out || (cap && !out)) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipSetDevice(e->device);
+    uint32_t count = 0;
+    const int rc = move_keys(e, n, key_hash, false, out, cap, &count);
+    if (rc != RL_OK) return rc;
+    *n_out = count;
+    return count > cap ? RL_E_TOO_LARGE : RL_OK;
+}
+
+extern "C" int rl_drop_keys(rl_engine* e, size_t n, const uint64_t* key_hash, uint64_t* n_dropped) {
+    if (!e || n > RL_MOVE_KEYS_MAX || (n && !key_hash)) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipSetDevice(e->device);
+    uint32_t count = 0;
+    const int rc = move_keys(e, n, key_hash, true, nullptr, 0, &count);
+    if (rc == RL_OK && n_dropped) *n_dropped = count;
+    return rc;
+}
+
+extern "C" int rl_put_keys(rl_engine* e, size_t n, const rl_key_image* in, size_t* n_put) {
+    if (!e || (n && !in)) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    for (size_t i = 0; i < n; ++i)
+        if (in[i].limiter >= e->lims.size()) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    std::vector<RegionImg> imgs(n);
+    for (size_t i = 0; i < n; ++i) {
+        RegionImg im = region_img(e, e->lims[in[i].limiter], mix64(in[i].key_hash));
+        im.s.a = in[i].word[0]; im.s.b = in[i].word[1]; im.s.c = in[i].word[2];
+        im.x = in[i].cache_word;
+        imgs[i] = im;
+    }
+    uint32_t fail = 0;
+    const int rc = apply_region_images(e, imgs, /*with_x=*/true, &fail);
+    if (rc != RL_OK) return rc;
+    if (n_put) *n_put = n - fail;
     return fail ? RL_E_CAPACITY : RL_OK;
 }
 

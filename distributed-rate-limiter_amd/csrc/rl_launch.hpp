@@ -333,8 +333,33 @@ struct ImportArgs {
     const uint64_t* xregion_addr;  // [n_groups] its local-cache words (0: none)
     const uint8_t* group_algo;     // [n_groups]
     const Slot* img;               // slot images, grouped by region
+    const uint64_t* xw;            // nullable: the images' local-cache words (rl_put_keys); the
+                                   // state import has none and writes 0
     uint32_t* fail;                // keys that found no free slot
 };
+
+// Key migration (rl_migrate.hip; rl_copy_keys / rl_drop_keys / rl_put_keys). KeyImage has the
+// layout of rl_key_image (include/rl_engine.h; static_assert in rl_engine.cpp): a slot's words
+// and its cache word as stored.
+struct KeyImage {
+    uint64_t key_hash;
+    uint64_t word[3];              // Slot a, b, c
+    uint64_t cache_word;
+    uint16_t limiter;
+    uint16_t reserved[3];
+};
+constexpr uint32_t kMoveKeysMax = 8192;   // RL_MOVE_KEYS_MAX
+struct MoveArgs {
+    const uint64_t* key;           // [n_keys] DISTINCT key hashes (pairs must not share a slot)
+    const DevLimiter* lims;
+    KeyImage* out;                 // [cap] the hits, in no order (nullable with cap 0)
+    uint32_t* count;               // += hits, those beyond cap included
+    uint32_t n_keys, n_lim, cap;
+    int shard_bits;
+};
+// one quad per (key, limiter) pair, n_keys x n_lim <= kMoveKeysMax x RL_MAX_LIMITERS of them;
+// drop: every hit's slot becomes a tombstone (key_hash 0 only in a launch of its own)
+hipError_t launch_move_keys(const MoveArgs& a, bool drop, hipStream_t s);
 
 hipError_t launch_export(const Slot* table, uint64_t n_slots, const DevLimiter& L, uint16_t lim,
                          int64_t now_ms, StateRec* out, uint32_t cap, uint32_t* count,
@@ -574,6 +599,10 @@ int route_pack_wire_mm(rl_engine* e, size_t n, const uint32_t* perm, const uint6
                        uint32_t* nparts, void* stream);
 int engine_device(rl_engine* e);
 size_t engine_max_batch(rl_engine* e);
+size_t engine_limiters(rl_engine* e);
+// The owner directory as installed (rl_set_owner_directory): its keys and their owners into
+// two arrays of kDirMax entries, in no order; returns the number of keys listed.
+size_t engine_directory(rl_engine* e, uint64_t* keys, uint32_t* owners);
 // Split router rounds: fold the engine's last batch status into acc on `stream` (after that
 // batch), and later settle the folded status of several batches at a step boundary: the
 // status those batches return together, with the table growth they asked for applied once.

@@ -579,7 +579,8 @@ __device__ inline void write_region(const RegionStage& S, Slot* tab, uint64_t* x
 
 // Import: one wave per region that receives entries. The region's present slots are
 // staged and rebuilt, then its keys are applied in order: replace the slot holding the
-// key's tag, else claim the first free slot of the key's probe sequence.
+// key's tag, else claim the first free slot of the key's probe sequence. rl_put_keys runs the
+// same kernel with the images' local-cache words (a.xw); the state import writes 0.
 __global__ __launch_bounds__(64) void k_import(ImportArgs a) {
     __shared__ RegionStage S;
     constexpr uint32_t NS = kRegionSlots;
@@ -608,7 +609,8 @@ __global__ __launch_bounds__(64) void k_import(ImportArgs a) {
             if (lane == 0) atomicAdd(a.fail, 1u);
         } else if (lane == 0) {
             S.occ[p] = kOccUsed;
-            S.tag[p] = im.tag; S.sa[p] = im.a; S.sb[p] = im.b; S.sc[p] = im.c; S.sx[p] = 0;
+            S.tag[p] = im.tag; S.sa[p] = im.a; S.sb[p] = im.b; S.sc[p] = im.c;
+            S.sx[p] = a.xw ? a.xw[j] : 0;             // (rl_put_keys carries the cache word)
         }
         wave_fence();
     }

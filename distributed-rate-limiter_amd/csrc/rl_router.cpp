@@ -31,6 +31,7 @@
 
 #include "../../include/rl_engine.h"
 #include "rl_launch.hpp"
+#include "rl_replan.hpp"
 
 using namespace rl;
 
@@ -89,6 +90,8 @@ struct rl_router {
     unsigned long long* acc = nullptr;   // split rounds: the rounds' engine statuses, folded on
                                          // device (kStatusAccWords), settled at the next step
     int64_t pub = RL_OK;                 // status this rank publishes in the next header
+    int64_t held = RL_OK;                // a step's status settled early by a re-plan: joins pub
+                                         // where the next step (or finish) would have settled it
     bool pending = false;                // the last engine batch's status is still to collect
     bool acc_pending = false;            // acc holds a split step's statuses to settle
     rl_router_stats st{};
@@ -291,7 +294,8 @@ extern "C" int rl_router_step(rl_router* r, size_t n, const uint64_t* key, const
     // published in the next header; the statuses received now (every rank's batch two steps
     // back) are the same on all ranks, so all fail together
     if (fatal(r->pub)) r->pub = RL_OK;              // delivered: every rank returns it now, once
-    r->pub = worse(r->pub, settle_pending(r));
+    r->pub = worse(r->pub, worse(r->held, settle_pending(r)));
+    r->held = RL_OK;
     // every rank sees every rank's capacities: a mismatch fails all of them here, before
     // any payload (all ranks must derive the same exchange plan)
     if (worst != RL_OK || cap_mismatch) {
@@ -418,7 +422,8 @@ extern "C" int rl_router_finish(rl_router* r) {
     // the last step may still run on the caller's stream (its return all-to-all and the
     // unpack that counts lost remainders): complete it before reading anything
     if (r->stepped) R_OK(hipEventSynchronize(r->done));
-    r->pub = worse(r->pub, settle_pending(r));
+    r->pub = worse(r->pub, worse(r->held, settle_pending(r)));
+    r->held = RL_OK;
     uint32_t lost = 0;
     R_OK(hipMemcpy(&lost, r->lost, 4, hipMemcpyDeviceToHost));
     if (lost) R_OK(hipMemset(r->lost, 0, 4));        // counted once: the next steps start clean
@@ -439,11 +444,12 @@ extern "C" int rl_router_finish(rl_router* r) {
     return (int)w;
 }
 
-extern "C" int rl_router_plan_directory(rl_router* r, size_t n, const uint64_t* key,
-                                        const uint64_t* count, uint64_t sampled, uint32_t k,
-                                        uint32_t* placed, void* stream) {
-    if (!r || (n && (!key || !count)) || n > kDirMax || k > kDirMax) return RL_E_INVALID_ARG;
-    hipStream_t s = stream ? (hipStream_t)stream : r->own;
+// The directory plan (DirPlan, rl_replan.hpp) shared by rl_router_plan_directory and
+// rl_router_replan_directory (collective): every rank's candidates merged, the k hottest kept
+// and placed on owners by longest-processing-time-first. Every rank computes the same plan;
+// nothing is installed.
+static int plan_directory(rl_router* r, size_t n, const uint64_t* key, const uint64_t* count,
+                          uint64_t sampled, uint32_t k, hipStream_t s, DirPlan* plan) {
     const uint32_t G = r->world;
     // exchange {n, sampled}, then every rank's candidates with every rank (all-gather), in
     // the buffer reserved at creation (no allocation between the two collectives)
@@ -486,39 +492,43 @@ extern "C" int rl_router_plan_directory(rl_router* r, size_t n, const uint64_t* 
     for (auto& x : v) hot += x.second;
     const double rest = total_sampled > hot ? (double)(total_sampled - hot) / G : 0.0;
     std::vector<double> load(G, rest);
-    std::vector<uint64_t> dk(v.size());
-    std::vector<uint32_t> dov(v.size());
+    plan->key.resize(v.size());
+    plan->owner.resize(v.size());
     for (size_t i = 0; i < v.size(); ++i) {
         uint32_t best = 0;
         for (uint32_t p = 1; p < G; ++p)
             if (load[p] < load[best]) best = p;
         load[best] += (double)v[i].second;
-        dk[i] = v[i].first;
-        dov[i] = best;
+        plan->key[i] = v[i].first;
+        plan->owner[i] = best;
     }
-    const int rc = rl_set_owner_directory(r->e, dk.size(), dk.data(), dov.data());
-    if (rc == RL_OK && placed) *placed = (uint32_t)dk.size();
+    return RL_OK;
+}
+
+extern "C" int rl_router_plan_directory(rl_router* r, size_t n, const uint64_t* key,
+                                        const uint64_t* count, uint64_t sampled, uint32_t k,
+                                        uint32_t* placed, void* stream) {
+    if (!r || (n && (!key || !count)) || n > kDirMax || k > kDirMax) return RL_E_INVALID_ARG;
+    DirPlan plan;
+    R_RC(plan_directory(r, n, key, count, sampled, k, stream ? (hipStream_t)stream : r->own, &plan));
+    const int rc = rl_set_owner_directory(r->e, plan.key.size(), plan.key.data(), plan.owner.data());
+    if (rc == RL_OK && placed) *placed = (uint32_t)plan.key.size();
     return rc;
 }
 
-extern "C" int rl_router_plan_directory_sampled(rl_router* r, size_t n, const uint64_t* key_hash,
-                                                uint32_t k, uint64_t min_count, uint32_t* placed,
-                                                void* stream) {
-    // argument errors, as rl_router_plan_directory's, return before the collective (every
-    // rank passes the same k and min_count)
-    if (!r || (n && !key_hash) || k == 0 || k > kDirMax || min_count == 0 || (uint64_t)n > (1ULL << 31))
-        return RL_E_INVALID_ARG;
-    hipStream_t s = stream ? (hipStream_t)stream : r->own;
-    // this rank's candidates land in the exchange buffer, which the plan below rewrites only
-    // after they are on the host: keys and counts where it puts its candidates ([2 kDirMax]),
-    // the header at the start of the receive area
+// This rank's top keys of a device sample, on the host (the candidates of the two _sampled
+// calls). A failure of this rank alone must not leave the others waiting in the collective
+// that follows: the caller goes on with no candidates and reports the status afterwards.
+static int sample_candidates(rl_router* r, size_t n, const uint64_t* key_hash, uint32_t k,
+                             uint64_t min_count, hipStream_t s, std::vector<uint64_t>* key,
+                             std::vector<uint64_t>* cnt) {
+    // the candidates land in the exchange buffer, which the plan rewrites only after they are
+    // on the host: keys and counts where it puts its candidates ([2 kDirMax]), the header at
+    // the start of the receive area
     uint64_t* dk = r->dir + 4 * (size_t)r->world;
     uint64_t* dc = dk + kDirMax;
     uint64_t* dh = dc + kDirMax;
     uint64_t hdr[4] = {0, 0, 0, 0};
-    std::vector<uint64_t> key, cnt;
-    // a failure of this rank alone must not leave the others waiting in the collective: it
-    // goes on with no candidates and reports afterwards
     int mine = rl_top_keys_device(r->e, n, key_hash, k, min_count, dk, dc, dh, s);
     if (mine == RL_OK) {
         if (hipMemcpyAsync(hdr, dh, sizeof(hdr), hipMemcpyDeviceToHost, s) != hipSuccess ||
@@ -530,16 +540,154 @@ extern "C" int rl_router_plan_directory_sampled(rl_router* r, size_t n, const ui
             mine = RL_E_INTERNAL;
     }
     if (mine == RL_OK && hdr[0]) {
-        key.resize(hdr[0]);
-        cnt.resize(hdr[0]);
-        if (hipMemcpy(key.data(), dk, hdr[0] * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(cnt.data(), dc, hdr[0] * 8, hipMemcpyDeviceToHost) != hipSuccess) {
+        key->resize(hdr[0]);
+        cnt->resize(hdr[0]);
+        if (hipMemcpy(key->data(), dk, hdr[0] * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(cnt->data(), dc, hdr[0] * 8, hipMemcpyDeviceToHost) != hipSuccess) {
             mine = RL_E_DEVICE;
-            key.clear();
-            cnt.clear();
+            key->clear();
+            cnt->clear();
         }
     }
+    return mine;
+}
+
+extern "C" int rl_router_plan_directory_sampled(rl_router* r, size_t n, const uint64_t* key_hash,
+                                                uint32_t k, uint64_t min_count, uint32_t* placed,
+                                                void* stream) {
+    // argument errors, as rl_router_plan_directory's, return before the collective (every
+    // rank passes the same k and min_count)
+    if (!r || (n && !key_hash) || k == 0 || k > kDirMax || min_count == 0 || (uint64_t)n > (1ULL << 31))
+        return RL_E_INVALID_ARG;
+    hipStream_t s = stream ? (hipStream_t)stream : r->own;
+    std::vector<uint64_t> key, cnt;
+    const int mine = sample_candidates(r, n, key_hash, k, min_count, s, &key, &cnt);
     const int rc = rl_router_plan_directory(r, key.size(), key.data(), cnt.data(), (uint64_t)n, k,
                                             placed, s);
     return mine != RL_OK ? mine : rc;
+}
+
+// ---------------------------------------------------------------- re-plan on a live router
+// (which keys move, and the images grouped by new owner: rl_replan.hpp)
+namespace {
+struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+};
+}  // namespace
+
+// One row of `words` u64 from every rank to every rank (through the exchange buffer's header
+// rows: words <= 2); got[p * words + w] = rank p's word w.
+static int gather_rows(rl_router* r, const uint64_t* mine, uint32_t words, std::vector<uint64_t>* got,
+                       hipStream_t s) {
+    const uint32_t G = r->world;
+    uint64_t* d = r->dir;
+    got->assign((size_t)G * words, 0);
+    const std::vector<uint64_t> sb(G, words), so(G, 0);
+    const std::vector<uint64_t> ro = offsets(sb);
+    R_OK(hipMemcpyAsync(d, mine, words * 8, hipMemcpyHostToDevice, s));
+    R_RC(a2av_at(r, d, so.data(), sb.data(), d + 2 * G, ro.data(), sb.data(), 8, s));
+    R_OK(hipMemcpyAsync(got->data(), d + 2 * G, (size_t)G * words * 8, hipMemcpyDeviceToHost, s));
+    R_OK(hipStreamSynchronize(s));
+    return RL_OK;
+}
+
+// `mine0`: a status of this rank from before the collective (its sample failed: it took part
+// with no candidates), returned after a re-plan that otherwise succeeded.
+static int replan(rl_router* r, size_t n, const uint64_t* key, const uint64_t* count, uint64_t sampled,
+                  uint32_t k, uint32_t* placed, uint64_t* moved, int mine0, hipStream_t s) {
+    const uint32_t G = r->world, me = r->rank;
+    rl_engine* e = r->e;
+    // 1. drain: this rank's previous step is complete, and its engine status is settled (the
+    // table growth it asked for applied) as the next step would have done; that step, or
+    // rl_router_finish, still publishes it, so it is reported when it would have been
+    if (r->stepped) R_OK(hipEventSynchronize(r->done));
+    r->held = worse(r->held, settle_pending(r));
+    // 2. plan D' and the movers from D to D' (the same on every rank)
+    DirPlan d_new, d_old;
+    R_RC(plan_directory(r, n, key, count, sampled, k, s, &d_new));
+    d_old.key.resize(kDirMax);
+    d_old.owner.resize(kDirMax);
+    const size_t n_old = engine_directory(e, d_old.key.data(), d_old.owner.data());
+    d_old.key.resize(n_old);
+    d_old.owner.resize(n_old);
+    const std::vector<Mover> M = mover_list(d_old, d_new, [&](uint64_t key) { return rl_owner_of(key, 0, G); });
+    const std::vector<uint64_t> mine_keys = movers_from(M, me);   // the movers this rank owns under D
+    // 3. copy my movers' images, grouped by new owner; counts, buffers, then a status row
+    int64_t local = RL_OK;
+    std::vector<rl_key_image> imgs(mine_keys.size() * std::max<size_t>(engine_limiters(e), 1));
+    size_t n_img = 0;
+    local = rl_copy_keys(e, mine_keys.size(), mine_keys.data(), imgs.data(), imgs.size(), &n_img);
+    if (local != RL_OK) n_img = 0;
+    imgs.resize(n_img);
+    const std::vector<uint64_t> sc = group_by_new_owner(&imgs, M, G);
+    std::vector<uint64_t> rc(G, 0);
+    {
+        const std::vector<uint64_t> one(G, 1);
+        uint64_t* d = r->dir;
+        R_OK(hipMemcpyAsync(d, sc.data(), G * 8, hipMemcpyHostToDevice, s));
+        R_RC(a2av(r, d, one, d + 2 * G, one, 8, s));
+        R_OK(hipMemcpyAsync(rc.data(), d + 2 * G, G * 8, hipMemcpyDeviceToHost, s));
+        R_OK(hipStreamSynchronize(s));
+    }
+    uint64_t n_recv = 0;
+    for (uint32_t p = 0; p < G; ++p) n_recv += rc[p];
+    DevBuf b_send, b_recv;                           // (freed on every way out)
+    (void)hipSetDevice(engine_device(e));
+    if (hipMalloc(&b_send.p, std::max<size_t>(n_img, 1) * sizeof(rl_key_image)) != hipSuccess ||
+        hipMalloc(&b_recv.p, std::max<size_t>(n_recv, 1) * sizeof(rl_key_image)) != hipSuccess)
+        local = worse(local, RL_E_NOMEM);
+    rl_key_image* d_send = (rl_key_image*)b_send.p;
+    rl_key_image* d_recv = (rl_key_image*)b_recv.p;
+    std::vector<uint64_t> row;
+    const uint64_t st1[2] = {(uint64_t)local, (uint64_t)n_img};
+    R_RC(gather_rows(r, st1, 2, &row, s));
+    int64_t worst = RL_OK;
+    uint64_t total = 0;
+    for (uint32_t p = 0; p < G; ++p) { worst = worse(worst, (int64_t)row[2 * p]); total += row[2 * p + 1]; }
+    if (worst != RL_OK) return (int)worst;           // nothing has changed; D stays installed
+    // 4. move: the images to their new owners, which put them; a second status row
+    std::vector<rl_key_image> got(n_recv);
+    if (n_img) R_OK(hipMemcpyAsync(d_send, imgs.data(), n_img * sizeof(rl_key_image), hipMemcpyHostToDevice, s));
+    R_RC(a2av(r, d_send, sc, d_recv, rc, sizeof(rl_key_image), s));
+    if (n_recv) R_OK(hipMemcpyAsync(got.data(), d_recv, n_recv * sizeof(rl_key_image), hipMemcpyDeviceToHost, s));
+    R_OK(hipStreamSynchronize(s));
+    local = rl_put_keys(e, got.size(), got.data(), nullptr);
+    const uint64_t st2[1] = {(uint64_t)local};
+    R_RC(gather_rows(r, st2, 1, &row, s));
+    for (uint32_t p = 0; p < G; ++p) worst = worse(worst, (int64_t)row[p]);
+    // 5. commit (the old owners drop their movers, every rank installs D'), or roll back (the
+    // new owners drop what they put: they held no state for those keys under D; D stays)
+    if (worst != RL_OK) {
+        std::vector<uint64_t> back(got.size());
+        for (size_t i = 0; i < got.size(); ++i) back[i] = got[i].key_hash;
+        std::sort(back.begin(), back.end());
+        back.erase(std::unique(back.begin(), back.end()), back.end());
+        const int drc = rl_drop_keys(e, back.size(), back.data(), nullptr);
+        return drc != RL_OK && !fatal(worst) ? drc : (int)worst;
+    }
+    R_RC(rl_drop_keys(e, mine_keys.size(), mine_keys.data(), nullptr));
+    R_RC(rl_set_owner_directory(e, d_new.key.size(), d_new.key.data(), d_new.owner.data()));
+    if (placed) *placed = (uint32_t)d_new.key.size();
+    if (moved) *moved = total;
+    return mine0;
+}
+
+extern "C" int rl_router_replan_directory(rl_router* r, size_t n, const uint64_t* key,
+                                          const uint64_t* count, uint64_t sampled, uint32_t k,
+                                          uint32_t* placed, uint64_t* moved, void* stream) {
+    if (!r || (n && (!key || !count)) || n > kDirMax || k > kDirMax) return RL_E_INVALID_ARG;
+    return replan(r, n, key, count, sampled, k, placed, moved, RL_OK, stream ? (hipStream_t)stream : r->own);
+}
+
+extern "C" int rl_router_replan_directory_sampled(rl_router* r, size_t n, const uint64_t* key_hash,
+                                                  uint32_t k, uint64_t min_count, uint32_t* placed,
+                                                  uint64_t* moved, void* stream) {
+    if (!r || (n && !key_hash) || k == 0 || k > kDirMax || min_count == 0 || (uint64_t)n > (1ULL << 31))
+        return RL_E_INVALID_ARG;
+    hipStream_t s = stream ? (hipStream_t)stream : r->own;
+    // the sample reads no limiter state, but it runs on the engine behind the previous step
+    std::vector<uint64_t> key, cnt;
+    const int mine = sample_candidates(r, n, key_hash, k, min_count, s, &key, &cnt);
+    return replan(r, key.size(), key.data(), cnt.data(), (uint64_t)n, k, placed, moved, mine, s);
 }

@@ -33,6 +33,7 @@ REM_UNKNOWN, REM_INVALID, REM_ERROR = -1, -2, -3
 RETRY_NEVER, RETRY_INVALID = -1, -2   # RL_RETRY_* (rl_retry_after)
 TOP_KEYS_MAX, TOP_KEYS_CANDIDATES = 4096, 65536   # RL_TOP_KEYS_* (rl_top_keys)
 USAGE_BINS, USAGE_CANDIDATES = 16, 65536   # RL_USAGE_* (rl_limiter_usage, rl_top_consumers)
+MOVE_KEYS_MAX = 8192                       # RL_MOVE_KEYS_MAX: keys per rl_copy_keys / rl_drop_keys
 OPT_STAGE_TIMING = 1
 OPT_PIPELINE = 2       # RL_OPT_PIPELINE: partition of batch k+1 overlaps batch k's decisions
 OPT_FIXED_CAPACITY = 4  # RL_OPT_FIXED_CAPACITY: no on-demand table growth
@@ -56,6 +57,8 @@ EXPORTS = [
     "rl_retry_after", "rl_retry_after_device",
     "rl_top_keys", "rl_top_keys_device", "rl_router_plan_directory_sampled",
     "rl_limiter_usage", "rl_top_consumers",
+    "rl_copy_keys", "rl_drop_keys", "rl_put_keys",
+    "rl_router_replan_directory", "rl_router_replan_directory_sampled",
 ]
 RCCL_EXPORTS = ["rl_rccl_unique_id", "rl_transport_rccl_create", "rl_transport_rccl_destroy"]
 STATE_SW_BUCKET, STATE_TB_BUCKET = 0, 1
@@ -102,6 +105,19 @@ class Usage(ctypes.Structure):
                                                  "exhausted_keys", "cache_blocked",
                                                  "used_permits")] + \
                [("hist", ctypes.c_uint64 * USAGE_BINS)]
+
+
+class KeyImage(ctypes.Structure):
+    """rl_key_image (include/rl_engine.h): one key's slot words and local-cache word as stored;
+    opaque except key_hash / limiter."""
+    _fields_ = [("key_hash", ctypes.c_uint64), ("word", ctypes.c_uint64 * 3),
+                ("cache_word", ctypes.c_uint64), ("limiter", ctypes.c_uint16),
+                ("reserved", ctypes.c_uint16 * 3)]
+
+
+KEY_IMAGE_DTYPE = np.dtype([("key_hash", "<u8"), ("word", "<u8", (3,)), ("cache_word", "<u8"),
+                            ("limiter", "<u2"), ("reserved", "<u2", (3,))])
+assert KEY_IMAGE_DTYPE.itemsize == ctypes.sizeof(KeyImage) == 48
 
 
 class TraceSpec(ctypes.Structure):
@@ -196,6 +212,14 @@ def lib():
     L.rl_top_consumers.argtypes = [vp, u16, i64, u32, i64, vp, vp, ctypes.POINTER(sz),
                                    ctypes.POINTER(ctypes.c_uint64)]
     L.rl_owner_of_engine.restype = u32
+    L.rl_copy_keys.argtypes = [vp, sz, vp, vp, sz, ctypes.POINTER(sz)]
+    L.rl_drop_keys.argtypes = [vp, sz, vp, ctypes.POINTER(ctypes.c_uint64)]
+    L.rl_put_keys.argtypes = [vp, sz, vp, ctypes.POINTER(sz)]
+    L.rl_router_replan_directory.argtypes = [vp, sz, vp, vp, ctypes.c_uint64, u32,
+                                             ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_uint64), vp]
+    L.rl_router_replan_directory_sampled.argtypes = [vp, sz, vp, u32, ctypes.c_uint64,
+                                                     ctypes.POINTER(u32),
+                                                     ctypes.POINTER(ctypes.c_uint64), vp]
     _lib = L
     return L
 
@@ -479,6 +503,46 @@ class Engine:
         n = ctypes.c_size_t(0)
         st = self._L.rl_import_state(self._h, _p(entries) if entries.shape[0] else None,
                                      entries.shape[0], ctypes.byref(n))
+        return st, n.value
+
+    def copy_keys(self, keys, cap=None):
+        """Images of the listed keys' state under every limiter (rl_copy_keys): a
+        KEY_IMAGE_DTYPE array sorted by (limiter, key_hash). Read-only. With `cap` the call is
+        made once with a buffer of that many images and returns (images, status, n_out)."""
+        keys = np.ascontiguousarray(keys, np.uint64)
+        n = ctypes.c_size_t(0)
+        kp = _p(keys) if keys.shape[0] else None
+        if cap is not None:
+            out = np.zeros(int(cap), KEY_IMAGE_DTYPE)
+            st = self._L.rl_copy_keys(self._h, keys.shape[0], kp, _p(out) if cap else None, int(cap),
+                                      ctypes.byref(n))
+            return out, st, n.value
+        out = np.zeros(keys.shape[0] * max(len(self.limiters), 1), KEY_IMAGE_DTYPE)
+        st = self._L.rl_copy_keys(self._h, keys.shape[0], kp, _p(out) if out.shape[0] else None,
+                                  out.shape[0], ctypes.byref(n))
+        if st != RL_OK:
+            raise RlError(st, "rl_copy_keys")
+        return out[:n.value]
+
+    def drop_keys(self, keys) -> int:
+        """Turn the listed keys' slots into tombstones (rl_drop_keys); returns the slots dropped."""
+        keys = np.ascontiguousarray(keys, np.uint64)
+        n = ctypes.c_uint64(0)
+        st = self._L.rl_drop_keys(self._h, keys.shape[0], _p(keys) if keys.shape[0] else None,
+                                  ctypes.byref(n))
+        if st != RL_OK:
+            raise RlError(st, "rl_drop_keys")
+        return n.value
+
+    def put_keys(self, images):
+        """Insert KEY_IMAGE_DTYPE images (rl_put_keys). Returns (status, images put); the status
+        is RL_OK or RL_E_CAPACITY, anything else raises."""
+        images = np.ascontiguousarray(images, KEY_IMAGE_DTYPE)
+        n = ctypes.c_size_t(0)
+        st = self._L.rl_put_keys(self._h, images.shape[0], _p(images) if images.shape[0] else None,
+                                 ctypes.byref(n))
+        if st not in (RL_OK, RL_E_CAPACITY):
+            raise RlError(st, "rl_put_keys")
         return st, n.value
 
     def sweep_expired(self, now_ns) -> int:

@@ -204,6 +204,33 @@ class CRouter:
             raise rl_amd.RlError(st, "rl_router_plan_directory_sampled")
         return placed.value
 
+    def replan_directory(self, keys, counts, sampled: int, k: int):
+        """plan_directory on a live router (collective, rl_router_replan_directory): the state
+        of every key that changes owner moves with it. Returns (placed, moved)."""
+        keys = np.ascontiguousarray(keys, np.uint64)
+        counts = np.ascontiguousarray(counts, np.uint64)
+        placed, moved = ctypes.c_uint32(0), ctypes.c_uint64(0)
+        st = self._L.rl_router_replan_directory(self._h, len(keys),
+                                                keys.ctypes.data if len(keys) else None,
+                                                counts.ctypes.data if len(counts) else None,
+                                                int(sampled), int(k), ctypes.byref(placed),
+                                                ctypes.byref(moved), None)
+        if st != rl_amd.RL_OK:
+            raise rl_amd.RlError(st, "rl_router_replan_directory")
+        return placed.value, moved.value
+
+    def replan_directory_sampled(self, keys, k: int, min_count: int, stream=None):
+        """plan_directory_sampled on a live router (collective,
+        rl_router_replan_directory_sampled). Returns (placed, moved)."""
+        placed, moved = ctypes.c_uint32(0), ctypes.c_uint64(0)
+        n = int(keys.numel())
+        st = self._L.rl_router_replan_directory_sampled(self._h, n, rl_amd._p(keys) if n else None,
+                                                        int(k), int(min_count), ctypes.byref(placed),
+                                                        ctypes.byref(moved), rl_amd._p(stream))
+        if st != rl_amd.RL_OK:
+            raise rl_amd.RlError(st, "rl_router_replan_directory_sampled")
+        return placed.value, moved.value
+
     def stats(self) -> dict:
         st = RouterStats()
         self._L.rl_router_stats_get(self._h, ctypes.byref(st))

@@ -355,6 +355,46 @@ int  rl_export_state(rl_engine* e, int64_t now_ns, rl_state_entry* out, size_t c
  * RL_E_CAPACITY: a region had no free slot (the other keys are imported). */
 int  rl_import_state(rl_engine* e, const rl_state_entry* in, size_t n, size_t* n_imported);
 
+/* ---- key migration: the state of a listed set of keys, bit for bit ------------------
+ * rl_export_state / rl_import_state move a whole keyspace in the Redis layout; these three move
+ * exactly the listed keys between engines (a hot-key directory that is re-planned on a live
+ * router, rl_router_replan_directory). An image is a key's slot as stored plus its local-cache
+ * word, so the receiving engine decides every later request of the key exactly as the sending
+ * one would have, a sliding-window key blocked by the local cache included. Images are opaque
+ * except key_hash / limiter and valid between engines with identical limiter lists. No `now` is
+ * involved: state that is dead by TTL travels as it is.
+ * All three take HOST buffers, run on the engine's stream behind every batch submitted before
+ * them (RL_OPT_PIPELINE included) and synchronise. They work on the table as installed (a growth
+ * the last batch asked for but nobody has collected is not applied, as rl_export_state), change
+ * no batch statistic, and neither change nor collect the status rl_last_status reports.
+ * RL_E_INVALID_ARG, before any device call and with every output untouched: a null engine
+ * (checked first), n > RL_MOVE_KEYS_MAX (copy / drop), n > 0 with a null array, a null n_out,
+ * cap > 0 with a null out, an image whose limiter the engine does not have (put). n == 0 is
+ * valid. */
+#define RL_MOVE_KEYS_MAX 8192               /* old + new directory */
+typedef struct rl_key_image {               /* 48 bytes */
+    uint64_t key_hash;
+    uint64_t word[3];                       /* the slot's state words as stored */
+    uint64_t cache_word;                    /* local-cache word, 0 without a cache table */
+    uint16_t limiter;
+    uint16_t reserved[3];
+} rl_key_image;
+/* Read-only. For every listed key (duplicates count once) and every limiter of the engine, one
+ * image if the key's slot holds state or a cache word; keys that were reset or never seen give
+ * none. Sorted by (limiter, key_hash as an unsigned value). *n_out = the exact count; when it
+ * exceeds cap nothing is written and RL_E_TOO_LARGE is returned. */
+int  rl_copy_keys(rl_engine* e, size_t n, const uint64_t* key_hash, rl_key_image* out, size_t cap,
+                  size_t* n_out);
+/* Removes what rl_copy_keys of the same list returns: each such slot becomes a tombstone (it
+ * keeps its place in its probe chain until a sweep or a crowded region load reclaims it).
+ * *n_dropped (nullable) = slots rewritten. */
+int  rl_drop_keys(rl_engine* e, size_t n, const uint64_t* key_hash, uint64_t* n_dropped);
+/* Inserts images, each into the region of its limiter that its key hashes to, replacing any
+ * state and cache word the key has there. There is no ownership check: the caller vouches that
+ * this engine owns the keys (multi-GPU: by hash or by the directory). RL_E_CAPACITY: a region
+ * had no free slot; the other images are put. *n_put (nullable) = images put. */
+int  rl_put_keys(rl_engine* e, size_t n, const rl_key_image* in, size_t* n_put);
+
 /* Background TTL sweep (Redis active expiry of the PEXPIRE deadlines set at
  * RedisRateLimitStorage.java:41-44 and Lua :64): frees every slot none of whose buckets is live at
  * now_ns, so table memory tracks live keys even for regions no batch touches. (Batches already
@@ -481,7 +521,9 @@ int  rl_route_unpack_return(rl_engine* e, size_t n, const uint32_t* perm, const 
  * Zipf traffic the hash owner of the top keys carries a multiple of the mean load (the top
  * key alone draws ~11% of all requests at s = 1.1); listing the hottest keys with owners
  * chosen to even the loads out removes that imbalance. Every rank must
- * install the same directory before any state exists for the listed keys. n = 0 clears. */
+ * install the same directory before any state exists for the listed keys. n = 0 clears.
+ * That restriction holds for rl_set_owner_directory / rl_router_plan_directory(_sampled) only:
+ * rl_router_replan_directory(_sampled) moves the keys' state and is legal on a live router. */
 int  rl_set_owner_directory(rl_engine* e, size_t n, const uint64_t* key_hash,
                             const uint32_t* owner);
 uint32_t rl_owner_of_engine(rl_engine* e, uint64_t key_hash);
@@ -571,6 +613,28 @@ int  rl_router_plan_directory(rl_router* r, size_t n, const uint64_t* key_hash,
 int  rl_router_plan_directory_sampled(rl_router* r, size_t n, const uint64_t* key_hash,
                                       uint32_t k, uint64_t min_count, uint32_t* placed,
                                       void* stream);
+/* The same two calls on a LIVE router (collective, legal at any point between steps): the new
+ * directory D' is planned as above and the state of every key whose owner differs between the
+ * installed directory D and D' (a key listed in neither has its hash owner) moves to its new
+ * owner with rl_copy_keys / rl_put_keys / rl_drop_keys, so the steps after it decide exactly as
+ * one engine on the concatenated stream would. n = 0 on every rank clears the directory and
+ * sends every listed key home. *placed = keys listed in D'; *moved = images that changed engine,
+ * summed over the ranks (the same on every rank); both nullable.
+ * The call first waits for this rank's previous step and settles its engine status as the next
+ * step would have (it is still returned by the same later step, or by rl_router_finish). Then
+ * every rank copies the movers it owns, the ranks exchange a status row (any failure: every
+ * rank returns it, nothing has changed), exchange the images, the new owners put them and the
+ * ranks exchange a second status row. All OK: the old owners drop their movers and every rank
+ * installs D'. Otherwise the new owners drop what they put, D stays installed and every rank
+ * returns the worst status (RL_E_CAPACITY: a receiving region of a fixed-capacity table was
+ * full). No path leaves a key's state on two engines or on none. Argument errors
+ * (RL_E_INVALID_ARG) are returned before any collective, as with the two calls above. */
+int  rl_router_replan_directory(rl_router* r, size_t n, const uint64_t* key_hash,
+                                const uint64_t* count, uint64_t sampled, uint32_t k,
+                                uint32_t* placed, uint64_t* moved, void* stream);
+int  rl_router_replan_directory_sampled(rl_router* r, size_t n, const uint64_t* key_hash,
+                                        uint32_t k, uint64_t min_count, uint32_t* placed,
+                                        uint64_t* moved, void* stream);
 void rl_router_destroy(rl_router* r);
 
 /* ---- synthetic traces (bench / tests; deterministic in (seed, index)) ------ */
