@@ -146,6 +146,10 @@ __host__ __device__ inline uint32_t region_local(uint64_t h, int shard_bits, int
     if (k == 0) return 0;
     return (uint32_t)((h << shard_bits) >> (64 - k));
 }
+// First slot of tag h's region in a table of 2^k regions (the cache words use the same index).
+__host__ __device__ inline size_t region_slot0(uint64_t h, int shard_bits, int k) {
+    return (size_t)region_local(h, shard_bits, k) * kRegionSlots;
+}
 
 __host__ __device__ inline int64_t floor_div_ms(int64_t ns) {
     int64_t q = ns / 1000000;
@@ -566,7 +570,7 @@ __device__ inline void sw_commit_allows(const DevLimiter& L, const SWGeo& g, uin
 
 // A slot is kept when the region is loaded iff some request at now >= batch_min could
 // still read it (x: its local-cache block-until, SW with the cache on); everything else is
-// dropped (the region is rebuilt in LDS).
+// dropped (the region is rebuilt in LDS). (The same rule per bucket: live_buckets, rl_table.hpp.)
 __device__ inline bool slot_live(const DevLimiter& L, const Slot& s, int64_t batch_min,
                                  uint64_t x = 0) {
     if (x != 0 && (int64_t)x > batch_min) return true;

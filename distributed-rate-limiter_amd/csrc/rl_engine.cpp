@@ -234,6 +234,45 @@ static int dalloc(T** p, size_t count) {
     return dalloc((void**)p, count * sizeof(T));
 }
 
+// A temporary device allocation, freed with the scope that owns it.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { dfree(p); }
+    int alloc(size_t count) { return dalloc(&p, count); }
+    operator T*() const { return p; }
+};
+
+// Orders the engine stream after the caller's work (construction; `err` says how that went)
+// and the caller's stream after ours (finish(), or the destructor on an early return). Does
+// nothing when the caller's stream is null or the engine's own.
+struct StreamJoin {
+    hipStream_t ours, user;
+    hipEvent_t ev = nullptr;
+    hipError_t err = hipSuccess;
+    StreamJoin(hipStream_t ours_, hipStream_t user_) : ours(ours_), user(user_) {
+        if (!user || user == ours) return;
+        err = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (err != hipSuccess) { ev = nullptr; return; }
+        err = hipEventRecord(ev, user);
+        if (err == hipSuccess) err = hipStreamWaitEvent(ours, ev, 0);
+    }
+    StreamJoin(const StreamJoin&) = delete;
+    StreamJoin& operator=(const StreamJoin&) = delete;
+    hipError_t finish() {
+        if (!ev) return hipSuccess;
+        hipError_t he = hipEventRecord(ev, ours);
+        if (he == hipSuccess) he = hipStreamWaitEvent(user, ev, 0);
+        (void)hipEventDestroy(ev);
+        ev = nullptr;
+        return he;
+    }
+    ~StreamJoin() { (void)finish(); }
+};
+
 extern "C" int rl_abi_version(void) { return RL_ABI_VERSION; }
 
 extern "C" const char* rl_strerror(int s) {
@@ -1023,6 +1062,20 @@ static int ensure_staging(rl_engine* e, size_t n) {
     return RL_OK;
 }
 
+// The host-buffer calls' requests into the staging arrays (limiter, op_or_skip: nullable).
+static int stage_requests(rl_engine* e, size_t n, const uint64_t* key, const int32_t* permits,
+                          const int64_t* now_ns, const uint16_t* limiter, const uint8_t* op_or_skip) {
+    const int rc = ensure_staging(e, n);
+    if (rc != RL_OK) return rc;
+    hipStream_t s = e->stream;
+    HIP_OK(hipMemcpyAsync(e->s_key, key, n * 8, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(e->s_permits, permits, n * 4, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(e->s_now, now_ns, n * 8, hipMemcpyHostToDevice, s));
+    if (limiter) HIP_OK(hipMemcpyAsync(e->s_lim, limiter, n * 2, hipMemcpyHostToDevice, s));
+    if (op_or_skip) HIP_OK(hipMemcpyAsync(e->s_op, op_or_skip, n, hipMemcpyHostToDevice, s));
+    return RL_OK;
+}
+
 extern "C" int rl_execute_batch(rl_engine* e, size_t n, const uint64_t* key,
                                 const int32_t* permits, const int64_t* now_ns,
                                 const uint16_t* limiter, const uint8_t* op, uint8_t* allowed,
@@ -1033,14 +1086,9 @@ extern "C" int rl_execute_batch(rl_engine* e, size_t n, const uint64_t* key,
     if (n == 0) return RL_OK;
     if (!key || !permits || !now_ns || !allowed || !remaining) return RL_E_INVALID_ARG;
     (void)hipSetDevice(e->device);
-    int rc = ensure_staging(e, n);
+    int rc = stage_requests(e, n, key, permits, now_ns, limiter, op);
     if (rc != RL_OK) return rc;
     hipStream_t s = e->stream;
-    HIP_OK(hipMemcpyAsync(e->s_key, key, n * 8, hipMemcpyHostToDevice, s));
-    HIP_OK(hipMemcpyAsync(e->s_permits, permits, n * 4, hipMemcpyHostToDevice, s));
-    HIP_OK(hipMemcpyAsync(e->s_now, now_ns, n * 8, hipMemcpyHostToDevice, s));
-    if (limiter) HIP_OK(hipMemcpyAsync(e->s_lim, limiter, n * 2, hipMemcpyHostToDevice, s));
-    if (op) HIP_OK(hipMemcpyAsync(e->s_op, op, n, hipMemcpyHostToDevice, s));
     rc = run_batch_device(e, n, e->s_key, e->s_permits, e->s_now, limiter ? e->s_lim : nullptr,
                           op ? e->s_op : nullptr, e->s_allowed, e->s_remaining,
                           tokens_after ? e->s_tokens : nullptr);
@@ -1170,20 +1218,11 @@ extern "C" int rl_retry_after_device(rl_engine* e, size_t n, const uint64_t* key
     if (n == 0) return RL_OK;
     if (!key_hash || !permits || !now_ns || !wait_ms) return RL_E_INVALID_ARG;
     (void)hipSetDevice(e->device);
-    hipStream_t user = (hipStream_t)stream;
-    if (user && user != e->stream) {
-        // order the engine stream after the caller's work, and the caller's after ours
-        hipEvent_t ev;
-        HIP_OK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        HIP_OK(hipEventRecord(ev, user));
-        HIP_OK(hipStreamWaitEvent(e->stream, ev, 0));
-        int rc = run_retry_device(e, n, key_hash, permits, now_ns, limiter, skip, wait_ms);
-        HIP_OK(hipEventRecord(ev, e->stream));
-        HIP_OK(hipStreamWaitEvent(user, ev, 0));
-        (void)hipEventDestroy(ev);
-        return rc;
-    }
-    return run_retry_device(e, n, key_hash, permits, now_ns, limiter, skip, wait_ms);
+    StreamJoin join(e->stream, (hipStream_t)stream);
+    HIP_OK(join.err);
+    const int rc = run_retry_device(e, n, key_hash, permits, now_ns, limiter, skip, wait_ms);
+    HIP_OK(join.finish());
+    return rc;
 }
 
 extern "C" int rl_retry_after(rl_engine* e, size_t n, const uint64_t* key_hash, const int32_t* permits,
@@ -1199,14 +1238,9 @@ extern "C" int rl_retry_after(rl_engine* e, size_t n, const uint64_t* key_hash, 
     // the table growth it asked for (rl_last_status returns that same status afterwards)
     const int st = collect_status(e);
     if (st == RL_E_DEVICE) return st;
-    int rc = ensure_staging(e, n);
+    int rc = stage_requests(e, n, key_hash, permits, now_ns, limiter, skip);
     if (rc != RL_OK) return rc;
     hipStream_t s = e->stream;
-    HIP_OK(hipMemcpyAsync(e->s_key, key_hash, n * 8, hipMemcpyHostToDevice, s));
-    HIP_OK(hipMemcpyAsync(e->s_permits, permits, n * 4, hipMemcpyHostToDevice, s));
-    HIP_OK(hipMemcpyAsync(e->s_now, now_ns, n * 8, hipMemcpyHostToDevice, s));
-    if (limiter) HIP_OK(hipMemcpyAsync(e->s_lim, limiter, n * 2, hipMemcpyHostToDevice, s));
-    if (skip) HIP_OK(hipMemcpyAsync(e->s_op, skip, n, hipMemcpyHostToDevice, s));
     rc = run_retry_device(e, n, e->s_key, e->s_permits, e->s_now, limiter ? e->s_lim : nullptr,
                           skip ? e->s_op : nullptr, e->s_remaining);
     if (rc != RL_OK) { (void)hipStreamSynchronize(s); return rc; }
@@ -1249,27 +1283,15 @@ extern "C" int rl_top_keys_device(rl_engine* e, size_t n, const uint64_t* key_ha
     TopkScratch sc;
     int rc = topk_scratch(e, &sc);
     if (rc != RL_OK) return rc;
-    hipStream_t user = (hipStream_t)stream;
-    const bool cross = user && user != e->stream;
-    hipEvent_t ev = nullptr;
-    if (cross) {
-        // order the engine stream after the caller's work, and the caller's after ours
-        HIP_OK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        hipError_t he = hipEventRecord(ev, user);
-        if (he == hipSuccess) he = hipStreamWaitEvent(e->stream, ev, 0);
-        if (he != hipSuccess) { (void)hipEventDestroy(ev); return RL_E_DEVICE; }
-    }
     hipStream_t s = e->stream;
-    hipError_t he = launch_topk_clear(sc, s);
-    if (he == hipSuccess) he = launch_topk_pass(sc, 0, key_hash, (uint32_t)n, min_count, s);
-    if (he == hipSuccess) he = launch_topk_pass(sc, 1, key_hash, (uint32_t)n, min_count, s);
-    if (he == hipSuccess) he = launch_topk_select(sc, k, min_count, n, top_key, top_count, hdr, s);
-    if (cross) {
-        if (he == hipSuccess) he = hipEventRecord(ev, s);
-        if (he == hipSuccess) he = hipStreamWaitEvent(user, ev, 0);
-        (void)hipEventDestroy(ev);
-    }
-    return he == hipSuccess ? RL_OK : RL_E_DEVICE;
+    StreamJoin join(s, (hipStream_t)stream);
+    HIP_OK(join.err);
+    HIP_OK(launch_topk_clear(sc, s));
+    HIP_OK(launch_topk_pass(sc, 0, key_hash, (uint32_t)n, min_count, s));
+    HIP_OK(launch_topk_pass(sc, 1, key_hash, (uint32_t)n, min_count, s));
+    HIP_OK(launch_topk_select(sc, k, min_count, n, top_key, top_count, hdr, s));
+    HIP_OK(join.finish());
+    return RL_OK;
 }
 
 extern "C" int rl_top_keys(rl_engine* e, size_t n, const uint64_t* key_hash, uint32_t k,
@@ -1939,42 +1961,28 @@ extern "C" int rl_export_state(rl_engine* e, int64_t now_ns, rl_state_entry* out
     (void)hipSetDevice(e->device);
     const int64_t now = floor_div_ms(now_ns);
     const uint32_t dcap = (uint32_t)std::min<size_t>(cap, 0xFFFFFFF0u);
-    StateRec* d_out = nullptr;
-    uint32_t* d_count = nullptr;
-    if (dalloc(&d_out, std::max<uint32_t>(dcap, 1u)) != RL_OK) return RL_E_NOMEM;
-    if (dalloc(&d_count, e->lims.size() + 1) != RL_OK) { dfree(d_out); return RL_E_NOMEM; }
-    int rc = RL_OK;
+    DevBuf<StateRec> d_out;
+    DevBuf<uint32_t> d_count;
+    if (d_out.alloc(std::max<uint32_t>(dcap, 1u)) != RL_OK || d_count.alloc(1) != RL_OK) return RL_E_NOMEM;
     uint32_t total = 0;
-    if (hipMemsetAsync(d_count, 0, sizeof(uint32_t), e->stream) != hipSuccess) rc = RL_E_DEVICE;
-    for (size_t li = 0; rc == RL_OK && li < e->lims.size(); ++li) {
+    HIP_OK(hipMemsetAsync(d_count, 0, sizeof(uint32_t), e->stream));
+    for (size_t li = 0; li < e->lims.size(); ++li) {
         const HostLimiter& h = e->lims[li];
-        if (launch_export((const Slot*)h.table, h.table_bytes / sizeof(Slot), h.dev, (uint16_t)li,
-                          now, d_out, dcap, d_count, e->stream) != hipSuccess)
-            rc = RL_E_DEVICE;
+        HIP_OK(launch_export((const Slot*)h.table, h.table_bytes / sizeof(Slot), h.dev, (uint16_t)li,
+                             now, d_out, dcap, d_count, e->stream));
     }
-    if (rc == RL_OK && (hipMemcpyAsync(&total, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                       e->stream) != hipSuccess ||
-                        hipStreamSynchronize(e->stream) != hipSuccess))
-        rc = RL_E_DEVICE;
-    if (rc == RL_OK) {
-        *n_out = total;
-        if (total > cap) {
-            rc = RL_E_TOO_LARGE;
-        } else if (total) {
-            if (hipMemcpy(out, d_out, (size_t)total * sizeof(StateRec), hipMemcpyDeviceToHost) != hipSuccess) {
-                rc = RL_E_DEVICE;
-            } else {
-                std::sort(out, out + total, [](const rl_state_entry& x, const rl_state_entry& y) {
-                    if (x.limiter != y.limiter) return x.limiter < y.limiter;
-                    if (x.key_hash != y.key_hash) return x.key_hash < y.key_hash;
-                    return x.window_start_ms < y.window_start_ms;
-                });
-            }
-        }
-    }
-    dfree(d_out);
-    dfree(d_count);
-    return rc;
+    HIP_OK(hipMemcpyAsync(&total, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    *n_out = total;
+    if (total > cap) return RL_E_TOO_LARGE;
+    if (total == 0) return RL_OK;
+    HIP_OK(hipMemcpy(out, d_out, (size_t)total * sizeof(StateRec), hipMemcpyDeviceToHost));
+    std::sort(out, out + total, [](const rl_state_entry& x, const rl_state_entry& y) {
+        if (x.limiter != y.limiter) return x.limiter < y.limiter;
+        if (x.key_hash != y.key_hash) return x.key_hash < y.key_hash;
+        return x.window_start_ms < y.window_start_ms;
+    });
+    return RL_OK;
 }
 
 // A slot image bound for the region at `addr` (its local-cache words at `xaddr`, 0: none), and
@@ -1986,12 +1994,11 @@ struct RegionImg { uint64_t addr, xaddr; uint8_t algo; Slot s; uint64_t x; };
 
 RegionImg region_img(const rl_engine* e, const HostLimiter& h, uint64_t tag) {
     RegionImg im{};
-    const uint32_t region = region_local(tag, e->shard_bits, h.dev.region_bits);
+    const size_t slot0 = region_slot0(tag, e->shard_bits, h.dev.region_bits);
     im.algo = (uint8_t)h.dev.algo;
     im.s.tag = tag;
-    im.addr = (uint64_t)(uintptr_t)h.table + (uint64_t)region * kRegionSlots * sizeof(Slot);
-    im.xaddr = h.cache_table ? (uint64_t)(uintptr_t)h.cache_table +
-                                   (uint64_t)region * kRegionSlots * sizeof(uint64_t) : 0;
+    im.addr = (uint64_t)(uintptr_t)((Slot*)h.table + slot0);
+    im.xaddr = h.cache_table ? (uint64_t)(uintptr_t)((uint64_t*)h.cache_table + slot0) : 0;
     return im;
 }
 
@@ -2017,38 +2024,31 @@ int apply_region_images(rl_engine* e, std::vector<RegionImg>& imgs, bool with_x,
     off.push_back((uint32_t)imgs.size());
     const size_t G = addr.size(), N = slots.size();
     const size_t bytes = N * sizeof(Slot) + N * 8 + G * 16 + (G + 1) * 4 + G + 16;
-    uint8_t* d = nullptr;
-    if (dalloc(&d, bytes) != RL_OK) return RL_E_NOMEM;
-    Slot* d_img = (Slot*)d;
-    uint64_t* d_xw = (uint64_t*)(d + N * sizeof(Slot));
+    DevBuf<uint8_t> d;
+    if (d.alloc(bytes) != RL_OK) return RL_E_NOMEM;
+    Slot* d_img = (Slot*)d.p;
+    uint64_t* d_xw = (uint64_t*)(d.p + N * sizeof(Slot));
     uint64_t* d_addr = d_xw + N;
     uint64_t* d_xaddr = d_addr + G;
     uint32_t* d_off = (uint32_t*)(d_xaddr + G);
     uint32_t* d_fail = d_off + G + 1;
     uint8_t* d_algo = (uint8_t*)(d_fail + 1);
-    int rc = RL_OK;
-    uint32_t fail = 0;
-    if (hipMemcpyAsync(d_img, slots.data(), N * sizeof(Slot), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-        (with_x && hipMemcpyAsync(d_xw, xw.data(), N * 8, hipMemcpyHostToDevice, e->stream) != hipSuccess) ||
-        hipMemcpyAsync(d_addr, addr.data(), G * 8, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-        hipMemcpyAsync(d_xaddr, xaddr.data(), G * 8, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-        hipMemcpyAsync(d_off, off.data(), (G + 1) * 4, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-        hipMemcpyAsync(d_algo, algo.data(), G, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-        hipMemsetAsync(d_fail, 0, 4, e->stream) != hipSuccess)
-        rc = RL_E_DEVICE;
-    if (rc == RL_OK) {
-        ImportArgs a{};
-        a.n_groups = (uint32_t)G; a.group_off = d_off; a.region_addr = d_addr; a.xregion_addr = d_xaddr;
-        a.group_algo = d_algo;
-        a.img = d_img; a.xw = with_x ? d_xw : nullptr; a.fail = d_fail;
-        if (launch_import(a, e->stream) != hipSuccess ||
-            hipMemcpyAsync(&fail, d_fail, 4, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-            hipStreamSynchronize(e->stream) != hipSuccess)
-            rc = RL_E_DEVICE;
-    }
-    (void)hipFree(d);
-    *fail_out = fail;
-    return rc;
+    hipStream_t s = e->stream;
+    HIP_OK(hipMemcpyAsync(d_img, slots.data(), N * sizeof(Slot), hipMemcpyHostToDevice, s));
+    if (with_x) HIP_OK(hipMemcpyAsync(d_xw, xw.data(), N * 8, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(d_addr, addr.data(), G * 8, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(d_xaddr, xaddr.data(), G * 8, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(d_off, off.data(), (G + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(d_algo, algo.data(), G, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemsetAsync(d_fail, 0, 4, s));
+    ImportArgs a{};
+    a.n_groups = (uint32_t)G; a.group_off = d_off; a.region_addr = d_addr; a.xregion_addr = d_xaddr;
+    a.group_algo = d_algo;
+    a.img = d_img; a.xw = with_x ? d_xw : nullptr; a.fail = d_fail;
+    HIP_OK(launch_import(a, s));
+    HIP_OK(hipMemcpyAsync(fail_out, d_fail, 4, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    return RL_OK;
 }
 }  // namespace
 
@@ -2150,48 +2150,36 @@ static int move_keys(rl_engine* e, size_t n, const uint64_t* key_hash, bool drop
     const size_t nk = keys.size(), n_lim = e->lims.size();
     if (nk == 0 || n_lim == 0) return RL_OK;
     const uint32_t dcap = drop ? 0u : (uint32_t)std::min<size_t>(cap, nk * n_lim);
-    uint64_t* d_keys = nullptr;
-    KeyImage* d_out = nullptr;
-    uint32_t* d_count = nullptr;
-    int rc = dalloc(&d_keys, nk);
-    if (rc == RL_OK) rc = dalloc(&d_out, std::max<uint32_t>(dcap, 1u));
-    if (rc == RL_OK) rc = dalloc(&d_count, 1);
+    DevBuf<uint64_t> d_keys;
+    DevBuf<KeyImage> d_out;
+    DevBuf<uint32_t> d_count;
+    if (d_keys.alloc(nk) != RL_OK || d_out.alloc(std::max<uint32_t>(dcap, 1u)) != RL_OK ||
+        d_count.alloc(1) != RL_OK)
+        return RL_E_NOMEM;
     hipStream_t s = e->stream;
-    if (rc == RL_OK && (hipMemcpyAsync(d_keys, keys.data(), nk * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-                        hipMemsetAsync(d_count, 0, sizeof(uint32_t), s) != hipSuccess))
-        rc = RL_E_DEVICE;
-    if (rc == RL_OK) {
-        MoveArgs a{};
-        a.key = d_keys; a.lims = e->d_lims; a.out = d_out; a.count = d_count;
-        a.n_keys = (uint32_t)nk; a.n_lim = (uint32_t)n_lim; a.cap = dcap; a.shard_bits = e->shard_bits;
-        hipError_t he = hipSuccess;
-        if (drop && keys[0] == 0) {                      // (sorted: key 0 comes first)
-            MoveArgs z = a;
-            z.n_keys = 1;
-            a.key = d_keys + 1; a.n_keys = (uint32_t)nk - 1;
-            he = launch_move_keys(a, true, s);
-            if (he == hipSuccess) he = launch_move_keys(z, true, s);
-        } else {
-            he = launch_move_keys(a, drop, s);
-        }
-        if (he != hipSuccess ||
-            hipMemcpyAsync(count, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            rc = RL_E_DEVICE;
+    HIP_OK(hipMemcpyAsync(d_keys, keys.data(), nk * 8, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemsetAsync(d_count, 0, sizeof(uint32_t), s));
+    MoveArgs a{};
+    a.key = d_keys; a.lims = e->d_lims; a.out = d_out; a.count = d_count;
+    a.n_keys = (uint32_t)nk; a.n_lim = (uint32_t)n_lim; a.cap = dcap; a.shard_bits = e->shard_bits;
+    if (drop && keys[0] == 0) {                          // (sorted: key 0 comes first)
+        MoveArgs z = a;
+        z.n_keys = 1;
+        a.key = d_keys + 1; a.n_keys = (uint32_t)nk - 1;
+        HIP_OK(launch_move_keys(a, true, s));
+        HIP_OK(launch_move_keys(z, true, s));
+    } else {
+        HIP_OK(launch_move_keys(a, drop, s));
     }
-    if (rc == RL_OK && !drop && *count && *count <= cap) {
-        if (*count > dcap) {
-            rc = RL_E_INTERNAL;                          // (more hits than pairs)
-        } else if (hipMemcpy(out, d_out, (size_t)*count * sizeof(KeyImage), hipMemcpyDeviceToHost) != hipSuccess) {
-            rc = RL_E_DEVICE;
-        } else {
-            std::sort(out, out + *count, [](const rl_key_image& x, const rl_key_image& y) {
-                return x.limiter != y.limiter ? x.limiter < y.limiter : x.key_hash < y.key_hash;
-            });
-        }
-    }
-    dfree(d_keys); dfree(d_out); dfree(d_count);
-    return rc;
+    HIP_OK(hipMemcpyAsync(count, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    if (drop || *count == 0 || *count > cap) return RL_OK;
+    if (*count > dcap) return RL_E_INTERNAL;             // (more hits than pairs)
+    HIP_OK(hipMemcpy(out, d_out, (size_t)*count * sizeof(KeyImage), hipMemcpyDeviceToHost));
+    std::sort(out, out + *count, [](const rl_key_image& x, const rl_key_image& y) {
+        return x.limiter != y.limiter ? x.limiter < y.limiter : x.key_hash < y.key_hash;
+    });
+    return RL_OK;
 }
 
 extern "C" int rl_copy_keys(rl_engine* e, size_t n, const uint64_t* key_hash, rl_key_image* out,
@@ -2242,23 +2230,17 @@ extern "C" int rl_sweep_expired(rl_engine* e, int64_t now_ns, uint64_t* reclaime
     std::lock_guard<std::mutex> lk(e->mu);
     (void)hipSetDevice(e->device);
     const int64_t now = floor_div_ms(now_ns);
-    uint32_t* d_count = nullptr;
-    if (dalloc(&d_count, e->lims.size() + 1) != RL_OK) return RL_E_NOMEM;
     std::vector<uint32_t> h(e->lims.size() + 1, 0);
-    int rc = RL_OK;
-    if (hipMemsetAsync(d_count, 0, h.size() * sizeof(uint32_t), e->stream) != hipSuccess) rc = RL_E_DEVICE;
-    for (size_t li = 0; rc == RL_OK && li < e->lims.size(); ++li) {
-        HostLimiter& hl = e->lims[li];
-        if (launch_sweep((Slot*)hl.table, hl.table_bytes / sizeof(Slot), hl.dev, now, d_count + li,
-                         e->stream) != hipSuccess)
-            rc = RL_E_DEVICE;
+    DevBuf<uint32_t> d_count;
+    if (d_count.alloc(h.size()) != RL_OK) return RL_E_NOMEM;
+    HIP_OK(hipMemsetAsync(d_count, 0, h.size() * sizeof(uint32_t), e->stream));
+    for (size_t li = 0; li < e->lims.size(); ++li) {
+        const HostLimiter& hl = e->lims[li];
+        HIP_OK(launch_sweep(hl.dev, hl.table_bytes / sizeof(Slot), now, d_count + li, e->stream));
     }
-    if (rc == RL_OK && (hipMemcpyAsync(h.data(), d_count, h.size() * sizeof(uint32_t),
-                                       hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-                        hipStreamSynchronize(e->stream) != hipSuccess))
-        rc = RL_E_DEVICE;
-    dfree(d_count);
-    if (rc == RL_OK && reclaimed)
+    HIP_OK(hipMemcpyAsync(h.data(), d_count, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    if (reclaimed)
         for (uint32_t c : h) *reclaimed += c;
-    return rc;
+    return RL_OK;
 }

@@ -367,8 +367,8 @@ hipError_t launch_export(const Slot* table, uint64_t n_slots, const DevLimiter& 
 hipError_t launch_import(const ImportArgs& a, hipStream_t s);
 hipError_t launch_grow(const Slot* old_tab, const uint64_t* old_x, Slot* new_tab, uint64_t* new_x,
                        uint64_t n_old_regions, int shard_bits, int k_new, int algo, hipStream_t s);
-hipError_t launch_sweep(Slot* table, uint64_t n_slots, const DevLimiter& L, int64_t now_ms,
-                        uint32_t* count, hipStream_t s);
+hipError_t launch_sweep(const DevLimiter& L, uint64_t n_slots, int64_t now_ms, uint32_t* count,
+                        hipStream_t s);                     // (L's own tables, n_slots of them)
 
 hipError_t launch_upsweep(const PartArgs& a, bool raw, bool wide, hipStream_t s);
 hipError_t launch_scatter(const PartArgs& a, bool raw, bool wide, hipStream_t s);

@@ -1,17 +1,13 @@
 // rl_migrate.hip — key migration: copy or drop the state of a listed set of keys, bit for bit
 // (rl_copy_keys / rl_drop_keys, include/rl_engine.h). The insert side, rl_put_keys, is the
-// state import's region rebuild with the cache word carried (k_import, rl_misc.hip).
+// state import's region rebuild with the cache word carried (k_import, rl_state.hip).
 //
 // The work is one lookup per (key, limiter) pair: pair p = key p / n_lim under limiter
-// p % n_lim, at most 8192 x 255 pairs per launch. Four lanes look one pair up, as
-// k_retry_after does: each lane loads one 32-B slot of the key's 4-slot bucket as two 16-B
-// loads (a probe step of a pair is one 128-B line) plus its cache word, the quad finds the
-// matching or the first free slot from the wave's ballots, and the probe walks on bucket by
-// bucket from slot_home until either shows up (rl_device.hpp: a key sits before the first free
-// slot of its probe sequence). A hit is emitted iff the slot holds state or a cache word, the
-// rule k_grow / k_import keep; tombstones and absent keys emit nothing. No `now` is involved:
-// state that is dead by TTL travels as it is. Hits are compacted through one counter with one
-// atomic per wave; the host sorts them.
+// p % n_lim, at most 8192 x 255 pairs per launch. Four lanes look one pair up with the quad
+// probe of rl_table.hpp, bucket by bucket from the key's home. A hit is emitted iff the slot
+// holds state or a cache word (slot_holds_state, the rule growth and import keep); tombstones
+// and absent keys emit nothing. No `now` is involved: state that is dead by TTL travels as it
+// is. Hits are compacted through one counter with one atomic per wave; the host sorts them.
 //
 // Drop: the lane that holds the hit rewrites its slot as a tombstone with plain vector stores
 // (tag kept, state words zero through slot_used, cache word zero). The host hands over distinct
@@ -23,64 +19,45 @@
 // the second 16 bytes instead, and a probe could read that half old and the rest new; the host
 // therefore drops key 0 in a launch of its own, in which each pair probes a different
 // limiter's table.
-#include "rl_kcommon.hpp"
+#include "rl_table.hpp"
 
 namespace rl {
 
 constexpr int kMoveThreads = 256;
 constexpr uint32_t kMoveBlockPairs = kMoveThreads / 4;
 
-typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
-
 template <bool DROP>
 __global__ __launch_bounds__(kMoveThreads) void k_move_keys(MoveArgs a) {
-    const uint32_t lane = threadIdx.x & 63, sub = lane & 3, qbase = lane & ~3u;
+    const uint32_t lane = threadIdx.x & 63, sub = lane & 3;
     const uint64_t n_pairs = (uint64_t)a.n_keys * a.n_lim;
     const uint64_t p = ((uint64_t)blockIdx.x * kMoveThreads + threadIdx.x) >> 2;   // this quad's pair
     bool op = p < n_pairs;                          // still probing
     uint64_t key = 0, h = 0;
     uint32_t lim = 0;
     int algo = 0;
-    RL_GLOBAL Slot* tab = nullptr;                  // the key's region (and its cache words)
-    RL_GLOBAL uint64_t* xtab = nullptr;
+    TableRegion R{nullptr, nullptr};                // the key's region (and its cache words)
     if (op) {
         key = a.key[p / a.n_lim];
         lim = (uint32_t)(p % a.n_lim);
         h = mix64(key);
         const DevLimiter& L = a.lims[lim];
         algo = L.algo;
-        const size_t r0 = (size_t)region_local(h, a.shard_bits, L.region_bits) * kRegionSlots;
-        tab = as_global((Slot*)L.table + r0);
-        xtab = L.cache_table ? as_global((uint64_t*)L.cache_table + r0) : nullptr;
+        R = table_region(L, h, a.shard_bits);
     }
-    const uint32_t home = slot_home(h);
-    u64x2_t lo{0, 0}, hi{0, 0};
-    uint64_t x = 0;
+    QuadSlot v{{0, 0}, {0, 0}, 0};
     uint32_t pos = 0;                               // < kRegionSlots: inside the region
     bool mine = false;                              // this lane holds the key's slot
     // (wave-uniform trip count; nearly always one. A full region without the key: absent)
-    for (uint32_t m = 0; m < kRegionSlots / 4; ++m) {
-        bool match = false, isfree = false;
+    for (uint32_t m = 0; m < kProbeBuckets; ++m) {
         if (op) {
-            pos = (home + 4 * m + sub) & (kRegionSlots - 1);
-            RL_GLOBAL const u64x2_t* sp = (RL_GLOBAL const u64x2_t*)(tab + pos);
-            lo = sp[0]; hi = sp[1];
-            x = xtab ? xtab[pos] : 0;
-            isfree = (lo.x | lo.y | hi.x | hi.y | x) == 0;
-            match = !isfree && lo.x == h;
+            pos = quad_pos(h, m, sub);
+            v = quad_load(R, pos);
         }
-        const uint32_t qm = (uint32_t)(__ballot(match) >> qbase) & 0xFu;
-        const uint32_t qf = (uint32_t)(__ballot(isfree) >> qbase) & 0xFu;
-        if (op && (qm | qf)) {
-            // a match after a free slot of the same bucket cannot be the key's (invariant)
-            const bool found = qm != 0 && (qf == 0 || __builtin_ctz(qm) < __builtin_ctz(qf));
-            mine = found && match && sub == (uint32_t)__builtin_ctz(qm);
-            op = false;
-        }
+        quad_resolve(op, v, h, lane, mine);
         if (!__any(op)) break;
     }
     // ---- the hits, compacted: one atomic per wave
-    const bool emit = mine && (x != 0 || state_present(algo, hi.x, hi.y));
+    const bool emit = mine && slot_holds_state(algo, Slot{v.lo.x, v.lo.y, v.hi.x, v.hi.y}, v.x);
     const uint64_t em = __ballot(emit);
     if (em == 0) return;                            // (wave-uniform)
     const int leader = __builtin_ctzll(em);
@@ -92,17 +69,17 @@ __global__ __launch_bounds__(kMoveThreads) void k_move_keys(MoveArgs a) {
     if (idx < a.cap) {
         KeyImage im{};
         im.key_hash = key;
-        im.word[0] = lo.y; im.word[1] = hi.x; im.word[2] = hi.y;
-        im.cache_word = x;
+        im.word[0] = v.lo.y; im.word[1] = v.hi.x; im.word[2] = v.hi.y;
+        im.cache_word = v.x;
         im.limiter = (uint16_t)lim;
         a.out[idx] = im;
     }
     if constexpr (DROP) {
         const Slot t = slot_used(Slot{h, 0, 0, 0});                // tag 0: c = kDeadMark
-        RL_GLOBAL u64x2_t* sp = (RL_GLOBAL u64x2_t*)(tab + pos);
+        RL_GLOBAL u64x2_t* sp = (RL_GLOBAL u64x2_t*)(R.tab + pos);
         sp[0] = u64x2_t{t.tag, t.a};
         sp[1] = u64x2_t{t.b, t.c};
-        if (xtab) xtab[pos] = 0;
+        if (R.xtab) R.xtab[pos] = 0;
     }
 }
 

@@ -1,5 +1,4 @@
-// rl_misc.hip — synthetic traces, multi-GPU routing kernels, state export / import /
-// growth / TTL sweep.
+// rl_misc.hip — synthetic traces, multi-GPU routing kernels, status kernels.
 #include "rl_kcommon.hpp"
 
 #pragma clang fp contract(off)
@@ -476,232 +475,6 @@ hipError_t launch_status_accum(const BatchCtl* ctl, unsigned long long flags, un
 hipError_t launch_counts_to_header(const uint32_t* counts, uint32_t g, int64_t* hdr, uint32_t stride,
                                    hipStream_t s) {
     hipLaunchKernelGGL(k_counts_to_header, dim3(1), dim3(64), 0, s, counts, g, hdr, stride);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------ state export / import
-// Export: one thread per slot of one limiter's table; every bucket live at `now` becomes one
-// Redis-layout entry (SW: "rl:<key>:<W>" counters, deadline last INCR + w; TB: "tb:<key>",
-// deadline last_refill + 2w), compacted through one counter. The host sorts the entries.
-__global__ __launch_bounds__(256) void k_export(const Slot* __restrict__ tab, uint64_t n_slots,
-                                                DevLimiter L, uint16_t lim, int64_t now,
-                                                StateRec* __restrict__ out, uint32_t cap,
-                                                uint32_t* count) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_slots) return;
-    const Slot v = tab[i];
-    StateRec r[2];
-    int m = 0;
-    const uint64_t key = unmix64(v.tag);
-    if (L.algo == kAlgoTB) {
-        if ((v.c & 1u) && !(now > (int64_t)v.b + L.ttl_ms)) {
-            StateRec& e = r[m++];
-            e = StateRec{};
-            e.key_hash = key; e.limiter = lim; e.kind = 1;
-            e.tokens = __longlong_as_double((long long)v.a);
-            e.last_refill_ms = (int64_t)v.b;
-            e.expire_at_ms = (int64_t)v.b + L.ttl_ms;
-        }
-    } else {
-        const SW2 q = sw_unpack(v.a, v.b, v.c);
-        const int64_t w = L.window_ms;
-        const int64_t d1 = q.b1_start + q.b1_off + w, d0 = q.b1_start + q.b0_off;
-        if (q.b0_cnt != 0 && !(now > d0)) {          // bucket b1_start - w (sorted first)
-            StateRec& e = r[m++];
-            e = StateRec{};
-            e.key_hash = key; e.limiter = lim; e.kind = 0;
-            e.window_start_ms = q.b1_start - w; e.count = q.b0_cnt; e.expire_at_ms = d0;
-        }
-        if (q.b1_cnt != 0 && !(now > d1)) {
-            StateRec& e = r[m++];
-            e = StateRec{};
-            e.key_hash = key; e.limiter = lim; e.kind = 0;
-            e.window_start_ms = q.b1_start; e.count = q.b1_cnt; e.expire_at_ms = d1;
-        }
-    }
-    if (m == 0) return;
-    const uint32_t k = atomicAdd(count, (uint32_t)m);
-    for (int j = 0; j < m; ++j)
-        if (k + (uint32_t)j < cap) out[k + j] = r[j];
-}
-
-// Whole-region rewrite shared by the state import and the TTL sweep: one wave stages the
-// region's 256 slots, keeps those `keep` accepts, rebuilds the probe chains in LDS
-// (linear probing from each key's home, as a batch's region load does) and later writes
-// every slot back, so the HBM slot invariant (rl_device.hpp, slot_free) holds afterwards.
-struct RegionStage {
-    alignas(16) uint64_t tag[kRegionSlots];
-    uint64_t sa[kRegionSlots], sb[kRegionSlots], sc[kRegionSlots], sx[kRegionSlots];
-    uint32_t occ[kRegionSlots];
-};
-
-template <class Keep>
-__device__ inline uint32_t stage_region(RegionStage& S, const Slot* tab, const uint64_t* xt,
-                                        uint32_t lane, Keep keep) {
-    constexpr uint32_t NS = kRegionSlots;
-    Slot img[NS / 64];
-    uint64_t xim[NS / 64];
-    bool kp[NS / 64];
-    uint32_t dropped = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < NS / 64; ++i) {
-        img[i] = tab[lane + 64 * i];
-        xim[i] = xt ? xt[lane + 64 * i] : 0;
-        kp[i] = !slot_free(img[i], xim[i]) && keep(img[i], xim[i]);
-        dropped += (!slot_free(img[i], xim[i]) && !kp[i]) ? 1u : 0u;
-        S.occ[lane + 64 * i] = 0;
-    }
-    wave_fence();
-#pragma unroll
-    for (uint32_t i = 0; i < NS / 64; ++i) {
-        if (!kp[i]) continue;
-        uint32_t p = slot_home(img[i].tag);
-        while (atomicCAS(&S.occ[p], 0u, 1u) != 0u) p = (p + 1) & (NS - 1);
-        S.tag[p] = img[i].tag; S.sa[p] = img[i].a; S.sb[p] = img[i].b; S.sc[p] = img[i].c;
-        S.sx[p] = xim[i];
-    }
-    wave_fence();
-    return dropped;
-}
-
-__device__ inline void write_region(const RegionStage& S, Slot* tab, uint64_t* xt, uint32_t lane) {
-    for (uint32_t k = lane; k < kRegionSlots; k += 64) {
-        Slot v{0, 0, 0, 0};
-        uint64_t x = 0;
-        if (S.occ[k] & kOccUsed) {
-            x = S.sx[k];
-            v = slot_used(Slot{S.tag[k], S.sa[k], S.sb[k], S.sc[k]}, x);
-        }
-        tab[k] = v;
-        if (xt) xt[k] = x;
-    }
-}
-
-// Import: one wave per region that receives entries. The region's present slots are
-// staged and rebuilt, then its keys are applied in order: replace the slot holding the
-// key's tag, else claim the first free slot of the key's probe sequence. rl_put_keys runs the
-// same kernel with the images' local-cache words (a.xw); the state import writes 0.
-__global__ __launch_bounds__(64) void k_import(ImportArgs a) {
-    __shared__ RegionStage S;
-    constexpr uint32_t NS = kRegionSlots;
-    const uint32_t g = blockIdx.x, lane = threadIdx.x;
-    if (g >= a.n_groups) return;
-    Slot* tab = (Slot*)(uintptr_t)a.region_addr[g];
-    const int algo = a.group_algo[g];
-    uint64_t* xt = (uint64_t*)(uintptr_t)a.xregion_addr[g];
-    stage_region(S, tab, xt, lane,
-                 [&](const Slot& v, uint64_t x) { return x != 0 || state_present(algo, v.b, v.c); });
-    for (uint32_t j = a.group_off[g]; j < a.group_off[g + 1]; ++j) {
-        const Slot im = a.img[j];
-        const uint32_t home = slot_home(im.tag);
-        int32_t p = -1;
-        for (uint32_t b = 0; b < NS / 64 && p < 0; ++b) {    // probe order = (b, lane)
-            const uint32_t s = (home + b * 64 + lane) & (NS - 1);
-            const bool used = (S.occ[s] & kOccUsed) != 0;
-            const uint64_t fre = __ballot(!used);
-            const uint64_t hit = __ballot(used && S.tag[s] == im.tag);
-            const uint64_t before = fre ? ((fre & (0 - fre)) - 1) | (fre & (0 - fre)) : ~0ULL;
-            const uint64_t h = hit & before;                  // a hit before the first free slot
-            if (h) p = (int32_t)((home + b * 64 + (uint32_t)__builtin_ctzll(h)) & (NS - 1));
-            else if (fre) p = (int32_t)((home + b * 64 + (uint32_t)__builtin_ctzll(fre)) & (NS - 1));
-        }
-        if (p < 0) {
-            if (lane == 0) atomicAdd(a.fail, 1u);
-        } else if (lane == 0) {
-            S.occ[p] = kOccUsed;
-            S.tag[p] = im.tag; S.sa[p] = im.a; S.sb[p] = im.b; S.sc[p] = im.c;
-            S.sx[p] = a.xw ? a.xw[j] : 0;             // (rl_put_keys carries the cache word)
-        }
-        wave_fence();
-    }
-    write_region(S, tab, xt, lane);
-}
-
-// Table growth (rl_grow_limiter): old region r of a limiter with 2^(k_new-1) regions splits
-// into new regions 2r and 2r+1 by the next tag bit (region_local with one more bit); every
-// slot holding state keeps its words and is re-inserted from its home in its new region.
-// One wave per old region; each new region is written whole (free slots as zeros).
-__global__ __launch_bounds__(64) void k_grow(const Slot* __restrict__ old_tab, const uint64_t* old_x,
-                                             Slot* __restrict__ new_tab, uint64_t* new_x,
-                                             uint64_t n_old, int shard_bits, int k_new, int algo) {
-    __shared__ RegionStage S[2];
-    constexpr uint32_t NS = kRegionSlots;
-    const uint32_t lane = threadIdx.x;
-    const uint64_t r = blockIdx.x;
-    if (r >= n_old) return;
-    Slot img[NS / 64];
-    uint64_t xim[NS / 64];
-    bool kp[NS / 64];
-#pragma unroll
-    for (uint32_t i = 0; i < NS / 64; ++i) {
-        img[i] = old_tab[r * NS + lane + 64 * i];
-        xim[i] = old_x ? old_x[r * NS + lane + 64 * i] : 0;
-        kp[i] = !slot_free(img[i], xim[i]) && (xim[i] != 0 || state_present(algo, img[i].b, img[i].c));
-        S[0].occ[lane + 64 * i] = 0;
-        S[1].occ[lane + 64 * i] = 0;
-    }
-    wave_fence();
-#pragma unroll
-    for (uint32_t i = 0; i < NS / 64; ++i) {
-        if (!kp[i]) continue;
-        RegionStage& T = S[region_local(img[i].tag, shard_bits, k_new) & 1u];
-        uint32_t p = slot_home(img[i].tag);
-        while (atomicCAS(&T.occ[p], 0u, 1u) != 0u) p = (p + 1) & (NS - 1);
-        T.tag[p] = img[i].tag; T.sa[p] = img[i].a; T.sb[p] = img[i].b; T.sc[p] = img[i].c;
-        T.sx[p] = xim[i];
-    }
-    wave_fence();
-    write_region(S[0], new_tab + (2 * r) * NS, new_x ? new_x + (2 * r) * NS : nullptr, lane);
-    write_region(S[1], new_tab + (2 * r + 1) * NS, new_x ? new_x + (2 * r + 1) * NS : nullptr, lane);
-}
-
-hipError_t launch_grow(const Slot* old_tab, const uint64_t* old_x, Slot* new_tab, uint64_t* new_x,
-                       uint64_t n_old_regions, int shard_bits, int k_new, int algo, hipStream_t s) {
-    if (n_old_regions == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_grow, dim3((uint32_t)n_old_regions), dim3(64), 0, s, old_tab, old_x, new_tab,
-                       new_x, n_old_regions, shard_bits, k_new, algo);
-    return hipGetLastError();
-}
-
-// TTL sweep: one wave per region; every used slot none of whose buckets is live at `now`
-// (slot_live, the criterion a batch's region load applies) is dropped and the region is
-// rebuilt (no tombstone survives a sweep). One counter atomic per wave.
-__global__ __launch_bounds__(64) void k_sweep(Slot* __restrict__ tab0, uint64_t n_regions,
-                                              DevLimiter L, int64_t now, uint32_t* count) {
-    __shared__ RegionStage S;
-    const uint32_t lane = threadIdx.x;
-    const uint64_t r = blockIdx.x;
-    if (r >= n_regions) return;
-    Slot* tab = tab0 + r * kRegionSlots;
-    uint64_t* xt = L.cache_table ? (uint64_t*)L.cache_table + r * kRegionSlots : nullptr;
-    uint32_t dead = stage_region(S, tab, xt, lane,
-                                 [&](const Slot& v, uint64_t x) { return slot_live(L, v, now, x); });
-    write_region(S, tab, xt, lane);
-    for (int o = 32; o > 0; o >>= 1) dead += __shfl_xor(dead, o, 64);
-    if (lane == 0 && dead) atomicAdd(count, dead);
-}
-
-hipError_t launch_sweep(Slot* table, uint64_t n_slots, const DevLimiter& L, int64_t now_ms,
-                        uint32_t* count, hipStream_t s) {
-    const uint64_t regions = n_slots / kRegionSlots;
-    if (regions == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_sweep, dim3((uint32_t)regions), dim3(64), 0, s, table, regions, L, now_ms,
-                       count);
-    return hipGetLastError();
-}
-
-hipError_t launch_export(const Slot* table, uint64_t n_slots, const DevLimiter& L, uint16_t lim,
-                         int64_t now_ms, StateRec* out, uint32_t cap, uint32_t* count,
-                         hipStream_t s) {
-    const uint64_t blocks = (n_slots + 255) / 256;
-    hipLaunchKernelGGL(k_export, dim3((uint32_t)blocks), dim3(256), 0, s, table, n_slots, L, lim,
-                       now_ms, out, cap, count);
-    return hipGetLastError();
-}
-
-hipError_t launch_import(const ImportArgs& a, hipStream_t s) {
-    if (a.n_groups == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_import, dim3(a.n_groups), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 

@@ -3,12 +3,10 @@
 // as it stands, without applying it (rl_retry_after, include/rl_engine.h).
 //
 // A read-only gather: no partition, no region image, no atomics, no table write. Four lanes
-// look one key up (16 keys per wave at a time): each lane loads one 32-B slot of the key's
-// 4-slot bucket as two 16-B loads, so a probe step of a query is one 128-B line, and the quad
-// finds the matching or the free slot from the wave's ballots. A wave takes 64 queries, so it
-// does four such steps with their loads in flight together; the slots then go to the lanes that
-// own the queries, and every lane searches for its own answer and stores it. The limiter table
-// sits in LDS (the only LDS use).
+// look one key up (16 keys per wave at a time) with the quad probe of rl_table.hpp. A wave takes
+// 64 queries, so it does four such steps with their home-bucket loads in flight together; the
+// slots then go to the lanes that own the queries, and every lane searches for its own answer
+// and stores it. The limiter table sits in LDS (the only LDS use).
 //
 // Both algorithms are monotone for a fixed state from the key's newest write on (the sliding
 // window's estimate never rises, the token balance never falls: DESIGN.md §4), so the answer
@@ -17,7 +15,7 @@
 // rl_device.hpp, the same code the region stage runs), and bisects with that predicate when
 // the guess is off by more than two. Guesses use any arithmetic; every returned value is one
 // the exact predicate confirmed at t and refuted at t - 1.
-#include "rl_kcommon.hpp"
+#include "rl_table.hpp"
 
 #pragma clang fp contract(off)
 
@@ -147,21 +145,7 @@ constexpr int kRetryBlockQueries = (kRetryThreads / 64) * kRetryWaveQueries;
 constexpr uint32_t kLimWords = sizeof(DevLimiter) / sizeof(uint64_t);
 static_assert(sizeof(DevLimiter) % sizeof(uint64_t) == 0, "DevLimiter is copied to LDS in 8-B words");
 
-typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
 enum : uint32_t { kZero = 0, kInvalid = 1, kNever = 2, kProbe = 3 };   // a query after its decode
-
-// The region of key tag h in limiter L's tables (the cache words only where L keeps a cache).
-struct RetryRegion {
-    RL_GLOBAL const Slot* tab;
-    RL_GLOBAL const uint64_t* xtab;
-};
-__device__ inline RetryRegion retry_region(const DevLimiter& L, uint64_t h, int shard_bits) {
-    const size_t r0 = (size_t)region_local(h, shard_bits, L.region_bits) * kRegionSlots;
-    RetryRegion R;
-    R.tab = as_global((const Slot*)L.table + r0);
-    R.xtab = L.cache_table ? as_global((const uint64_t*)L.cache_table + r0) : nullptr;
-    return R;
-}
 
 // a[k] = a[k + 1]: the per-query loop below always works on element 0 and shifts the rest
 // down, so the arrays stay in registers (constant indices) and the loop body exists once
@@ -182,7 +166,7 @@ __global__ __launch_bounds__(kRetryThreads, 4) void k_retry_after(RetryArgs a) {
     extern __shared__ uint64_t s_limw[];
     const DevLimiter* s_lims = (const DevLimiter*)s_limw;
     constexpr int Q = kRetryPerQuad;
-    const uint32_t lane = threadIdx.x & 63, sub = lane & 3, qbase = lane & ~3u;
+    const uint32_t lane = threadIdx.x & 63, sub = lane & 3;
     const uint32_t q = blockIdx.x * kRetryBlockQueries + threadIdx.x;      // this lane's query
     // ---- the request (a skipped one touches no table)
     uint64_t key = 0;
@@ -213,22 +197,15 @@ __global__ __launch_bounds__(kRetryThreads, 4) void k_retry_after(RetryArgs a) {
     // ---- the home buckets of all four steps, loaded together
     uint32_t stq[Q];                     // the served query's limiter << 2 | code
     uint64_t hq[Q];
-    u64x2_t lo2[Q], hi2[Q];
-    uint64_t xw[Q];
+    QuadSlot vq[Q];
 #pragma unroll
     for (int j = 0; j < Q; ++j) {
         const int owner = 16 * j + (int)(lane >> 2);
         hq[j] = (uint64_t)shfl64((int64_t)h, owner);
         stq[j] = (uint32_t)__shfl((int)st, owner, 64);
-        lo2[j] = hi2[j] = u64x2_t{0, 0};
-        xw[j] = 0;
-        if ((stq[j] & 3u) == kProbe) {
-            const RetryRegion R = retry_region(s_lims[stq[j] >> 2], hq[j], a.shard_bits);
-            const uint32_t pos = (slot_home(hq[j]) + sub) & (kRegionSlots - 1);   // < 256: in the region
-            RL_GLOBAL const u64x2_t* sp = (RL_GLOBAL const u64x2_t*)(R.tab + pos);
-            lo2[j] = sp[0]; hi2[j] = sp[1];
-            if (R.xtab) xw[j] = R.xtab[pos];
-        }
+        vq[j] = QuadSlot{{0, 0}, {0, 0}, 0};
+        if ((stq[j] & 3u) == kProbe)
+            vq[j] = quad_load(table_region(s_lims[stq[j] >> 2], hq[j], a.shard_bits), quad_pos(hq[j], 0, sub));
     }
     // ---- per step (one copy of this code: it works on element 0 and shifts the others down):
     // the keys' slots, handed to the lanes that own the queries
@@ -238,49 +215,30 @@ __global__ __launch_bounds__(kRetryThreads, 4) void k_retry_after(RetryArgs a) {
     for (int j = 0; j < Q; ++j) {
         bool op = (stq[0] & 3u) == kProbe;         // still probing
         const uint64_t hj = hq[0];
-        u64x2_t lo = lo2[0], hi = hi2[0];
-        uint64_t x = xw[0];
+        QuadSlot v = vq[0];
         bool mine = false;                         // this lane holds the key's slot
-        // linear probing over 4-slot buckets from the home, wrapping inside the region; the key
-        // sits before the first free slot of its probe sequence (rl_device.hpp)
+        // the quad probe (rl_table.hpp) from the preloaded home bucket on
         for (uint32_t m = 0;; ++m) {               // (wave-uniform trip count; nearly always one)
-            bool match = false, isfree = false;
-            if (op) {
 #ifdef RL_RETRY_COUNT
-                if (a.dbg && sub == 0) atomicAdd(a.dbg + 2, 1ULL);
+            if (op && a.dbg && sub == 0) atomicAdd(a.dbg + 2, 1ULL);
 #endif
-                isfree = (lo.x | lo.y | hi.x | hi.y | x) == 0;
-                match = !isfree && lo.x == hj;
-            }
-            const uint32_t qm = (uint32_t)(__ballot(match) >> qbase) & 0xFu;
-            const uint32_t qf = (uint32_t)(__ballot(isfree) >> qbase) & 0xFu;
-            if (op && (qm | qf)) {
-                // a match after a free slot of the same bucket cannot be the key's (invariant)
-                const bool found = qm != 0 && (qf == 0 || __builtin_ctz(qm) < __builtin_ctz(qf));
-                mine = found && match && sub == (uint32_t)__builtin_ctz(qm);
-                op = false;
-            }
-            if (m + 1 == kRegionSlots / 4) op = false;         // a full region without the key: absent
+            quad_resolve(op, v, hj, lane, mine);
+            if (m + 1 == kProbeBuckets) op = false;            // a full region without the key: absent
             if (!__any(op)) break;
-            if (op) {                              // the next bucket
-                const RetryRegion R = retry_region(s_lims[stq[0] >> 2], hj, a.shard_bits);
-                const uint32_t pos = (slot_home(hj) + 4 * (m + 1) + sub) & (kRegionSlots - 1);
-                RL_GLOBAL const u64x2_t* sp = (RL_GLOBAL const u64x2_t*)(R.tab + pos);
-                lo = sp[0]; hi = sp[1];
-                x = R.xtab ? R.xtab[pos] : 0;
-            }
+            if (op)                                // the next bucket
+                v = quad_load(table_region(s_lims[stq[0] >> 2], hj, a.shard_bits), quad_pos(hj, m + 1, sub));
         }
         // lane 16 j + k takes the slot that quad k found (at most one lane of a quad has one)
         const uint64_t mm = __ballot(mine);
         const uint32_t nib = (uint32_t)(mm >> (4 * (lane & 15u))) & 0xFu;    // quad (lane & 15)'s lanes
         const int from = (int)(4 * (lane & 15u)) + (nib ? __builtin_ctz(nib) : 0);
-        const uint64_t ta = (uint64_t)shfl64((int64_t)lo.y, from);
-        const uint64_t tb = (uint64_t)shfl64((int64_t)hi.x, from);
-        const uint64_t tc = (uint64_t)shfl64((int64_t)hi.y, from);
+        const uint64_t ta = (uint64_t)shfl64((int64_t)v.lo.y, from);
+        const uint64_t tb = (uint64_t)shfl64((int64_t)v.hi.x, from);
+        const uint64_t tc = (uint64_t)shfl64((int64_t)v.hi.y, from);
         uint64_t tx = 0;
-        if (__any(mine && x != 0)) tx = (uint64_t)shfl64((int64_t)x, from);   // (cache-on limiters only)
+        if (__any(mine && v.x != 0)) tx = (uint64_t)shfl64((int64_t)v.x, from);   // (cache-on limiters only)
         if ((int)(lane >> 4) == j && nib != 0) { va = ta; vb = tb; vc = tc; vx = tx; have = true; }
-        shift_down(stq); shift_down(hq); shift_down(lo2); shift_down(hi2); shift_down(xw);
+        shift_down(stq); shift_down(hq); shift_down(vq);
     }
     // ---- the answer (skipped 0, invalid, never; an absent key grants any p <= max at once: 0)
     int64_t out = code == kInvalid ? kRetryInvalid : code == kNever ? kRetryNever : 0;

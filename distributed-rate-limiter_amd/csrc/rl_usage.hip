@@ -5,7 +5,8 @@
 // Every kernel here is one read-only pass over the limiter's slots (grid-stride, a wave takes
 // 64 consecutive slots = 2 KB at a time) that evaluates each slot with the engine's own peek
 // code (tb_step / sw_step with kOpPeek, rl_device.hpp): the numbers are what RL_OP_PEEK would
-// return for every key at `now`. No table word, cache word or batch scratch is written.
+// return for every key at `now`, for the slots live_buckets (rl_table.hpp) finds alive. No table
+// word, cache word or batch scratch is written.
 //
 //   k_usage_census   the ~22 counters of rl_usage. Lanes keep their own sums over the whole
 //                    loop (histogram bin b lives in lane b: one ballot + popcount per bin and
@@ -25,7 +26,7 @@
 //                    atomic per wave and step.
 // The host (rl_engine.cpp) drives the passes, reads the histogram between them and orders the
 // candidates.
-#include "rl_kcommon.hpp"
+#include "rl_table.hpp"
 
 #pragma clang fp contract(off)
 
@@ -46,21 +47,18 @@ struct UsageEval {
     int64_t used;            // live (redis != 0): max - clamp(available, 0, max)
 };
 
-// The liveness rule is k_export's; `available` is the peek of the shared step functions.
+// Liveness is live_buckets (rl_table.hpp); `available` is the peek of the shared step functions.
 __device__ inline UsageEval usage_eval(const DevLimiter& L, const Slot& v, uint64_t x, int64_t now) {
     UsageEval u;
     u.used_slot = !slot_free(v, x);
     u.blocked = x != 0 && now < (int64_t)x;
     u.used = 0;
     int64_t avail = 0;
-    if (L.algo == kAlgoTB) {
-        u.redis = ((v.c & 1u) && !(now > (int64_t)v.b + L.ttl_ms)) ? 1u : 0u;
+    if (L.algo == kAlgoTB) {       // (live_buckets inside the branch: it folds to this algorithm's rule)
+        u.redis = live_buckets(L, v, now).n;
         if (u.redis) avail = tb_step(L, kOpPeek, 1, now, v.a, v.b, v.c).remaining;
     } else {
-        const SW2 q = sw_unpack(v.a, v.b, v.c);
-        const int64_t w = L.window_ms;
-        const int64_t d1 = q.b1_start + q.b1_off + w, d0 = q.b1_start + q.b0_off;
-        u.redis = ((q.b0_cnt != 0 && !(now > d0)) ? 1u : 0u) + ((q.b1_cnt != 0 && !(now > d1)) ? 1u : 0u);
+        u.redis = live_buckets(L, v, now).n;
         if (u.redis) avail = sw_step(L, kOpPeek, 1, now, v.a, v.b, v.c).remaining;
     }
     if (u.redis) {
