@@ -18,6 +18,7 @@
 
 #include "../../include/rl_engine.h"
 #include "rl_launch.hpp"
+#include "rl_snapshot.hpp"
 
 using namespace rl;
 
@@ -194,6 +195,11 @@ struct rl_engine {
     void* topk = nullptr;                   // rl_top_keys scratch (topk_scratch_bytes), on first use
     void* usage = nullptr;                  // rl_limiter_usage / rl_top_consumers scratch, on first use
     uint32_t usage_passes = 0;              // table passes of the last rl_top_consumers (rl_debug_fetch)
+    void* snap = nullptr;                   // snapshot / ordered-put scratch (snap_scratch_bytes), on first use
+    uint32_t* put_heads = nullptr;          // [put_heads_cap] run heads of an ordered put
+    size_t put_heads_cap = 0;
+    KeyImage* img_stage = nullptr;          // [img_stage_cap] images of rl_snapshot_keys / rl_restore_keys
+    size_t img_stage_cap = 0;
 };
 
 #define HIP_OK(x)                                                      \
@@ -396,6 +402,7 @@ extern "C" void rl_destroy(rl_engine* e) {
     dfree(e->route_list); dfree(e->route_start); dfree(e->route_cnt);
     dfree(e->order); dfree(e->order_meta); dfree(e->solo_list);
     dfree(e->d_stats); dfree(e->retry_dbg); dfree(e->topk); dfree(e->usage);
+    dfree(e->snap); dfree(e->put_heads); dfree(e->img_stage);
     dfree(e->s_key); dfree(e->s_permits); dfree(e->s_now); dfree(e->s_lim); dfree(e->s_op);
     dfree(e->s_allowed); dfree(e->s_remaining); dfree(e->s_tokens);
     dfree(e->route_scratch); dfree(e->route_counts); dfree(e->d_dir);
@@ -2204,12 +2211,9 @@ extern "C" int rl_drop_keys(rl_engine* e, size_t n, const uint64_t* key_hash, ui
     return rc;
 }
 
-extern "C" int rl_put_keys(rl_engine* e, size_t n, const rl_key_image* in, size_t* n_put) {
-    if (!e || (n && !in)) return RL_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    for (size_t i = 0; i < n; ++i)
-        if (in[i].limiter >= e->lims.size()) return RL_E_INVALID_ARG;
-    (void)hipSetDevice(e->device);
+// rl_put_keys with the engine locked and every image's limiter known to exist: the images
+// grouped by region on the host, then k_import. *fail = images that found no free slot.
+static int put_images_host(rl_engine* e, size_t n, const rl_key_image* in, uint32_t* fail) {
     std::vector<RegionImg> imgs(n);
     for (size_t i = 0; i < n; ++i) {
         RegionImg im = region_img(e, e->lims[in[i].limiter], mix64(in[i].key_hash));
@@ -2217,11 +2221,194 @@ extern "C" int rl_put_keys(rl_engine* e, size_t n, const rl_key_image* in, size_
         im.x = in[i].cache_word;
         imgs[i] = im;
     }
+    return apply_region_images(e, imgs, /*with_x=*/true, fail);
+}
+
+extern "C" int rl_put_keys(rl_engine* e, size_t n, const rl_key_image* in, size_t* n_put) {
+    if (!e || (n && !in)) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    for (size_t i = 0; i < n; ++i)
+        if (in[i].limiter >= e->lims.size()) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
     uint32_t fail = 0;
-    const int rc = apply_region_images(e, imgs, /*with_x=*/true, &fail);
+    const int rc = put_images_host(e, n, in, &fail);
     if (rc != RL_OK) return rc;
     if (n_put) *n_put = n - fail;
     return fail ? RL_E_CAPACITY : RL_OK;
+}
+
+// ---------------------------------------------------------------- snapshot / restore
+// rl_snapshot_keys(_device), rl_put_keys_device, rl_restore_keys (rl_snapshot.hip; the cut rule
+// and ordered form: rl_snapshot.hpp). Like the migration calls they run on the engine stream
+// behind every batch submitted before them, work on the table as installed (no collect_status,
+// no growth) and touch no batch scratch, d_stats, d_ctl or status word; what the comment above
+// says about a put between two batches holds for a whole table of them.
+// Device memory, all of it allocated on first use and freed by rl_destroy:
+//   e->snap       snap_scratch_bytes() = 8 B per region of a call (kSnapMaxRegions of them) + 48 B
+//                 = 512 KiB, whatever the table's size
+//   e->put_heads  4 B per image of the largest put so far (the host form: <= max_batch images)
+//   e->img_stage  the host forms' images: min(cap, regions of the call x 256) (snapshot) or
+//                 min(n, max_batch) (restore) x 48 B, the largest so far
+static_assert(RL_SNAPSHOT_MIN_CAP == kSnapRegionSlots && RL_SNAPSHOT_MIN_CAP == kRegionSlots,
+              "a cap of one region always makes progress");
+
+static int snap_scratch(rl_engine* e, SnapScratch* sc) {
+    if (!e->snap) {
+        int rc = dalloc(&e->snap, snap_scratch_bytes());
+        if (rc != RL_OK) return rc;
+    }
+    *sc = snap_scratch_at(e->snap);
+    return RL_OK;
+}
+
+// (growing either buffer frees the old one, which waits for the device: nothing still reads it)
+static int ensure_put_heads(rl_engine* e, size_t n) {
+    if (n <= e->put_heads_cap) return RL_OK;
+    dfree(e->put_heads);
+    e->put_heads_cap = 0;
+    int rc = dalloc(&e->put_heads, n);
+    if (rc == RL_OK) e->put_heads_cap = n;
+    return rc;
+}
+
+static int ensure_img_stage(rl_engine* e, size_t n) {
+    if (n <= e->img_stage_cap) return RL_OK;
+    dfree(e->img_stage);
+    e->img_stage_cap = 0;
+    int rc = dalloc(&e->img_stage, n);
+    if (rc == RL_OK) e->img_stage_cap = n;
+    return rc;
+}
+
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+// The three snapshot launches for limiter `li` on the engine stream; *m_out = regions handled.
+static int snapshot_enqueue(rl_engine* e, size_t li, uint64_t region_begin, uint64_t region_count,
+                            KeyImage* out, uint64_t cap, uint64_t* hdr, const SnapScratch& sc,
+                            uint64_t* m_out) {
+    const HostLimiter& h = e->lims[li];
+    SnapArgs a{};
+    a.L = h.dev;
+    a.lim = (uint32_t)li;
+    a.regions_total = h.table_bytes / sizeof(Slot) / kRegionSlots;
+    a.region_begin = region_begin;
+    a.m = (uint32_t)snap_clip(region_begin, region_count, a.regions_total);
+    a.cap = std::min<uint64_t>(cap, kSnapMaxImages);
+    a.count = sc.count; a.offset = sc.offset; a.out = out; a.hdr = hdr;
+    if (m_out) *m_out = a.m;
+    HIP_OK(launch_snapshot(a, e->stream));
+    return RL_OK;
+}
+
+extern "C" int rl_snapshot_keys_device(rl_engine* e, uint16_t limiter, uint64_t region_begin,
+                                       uint64_t region_count, rl_key_image* out, size_t cap,
+                                       uint64_t* hdr, void* stream) {
+    if (!e || !hdr || (cap && !out) || !aligned16(out)) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (limiter >= e->lims.size()) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    SnapScratch sc;
+    int rc = snap_scratch(e, &sc);
+    if (rc != RL_OK) return rc;
+    StreamJoin join(e->stream, (hipStream_t)stream);
+    HIP_OK(join.err);
+    rc = snapshot_enqueue(e, limiter, region_begin, region_count, (KeyImage*)out, cap, hdr, sc, nullptr);
+    if (rc != RL_OK) return rc;
+    HIP_OK(join.finish());
+    return RL_OK;
+}
+
+extern "C" int rl_snapshot_keys(rl_engine* e, uint16_t limiter, uint64_t region_begin,
+                                uint64_t region_count, rl_key_image* out, size_t cap, size_t* n_out,
+                                uint64_t* regions_done, uint64_t* regions_total) {
+    if (!e || !n_out || !regions_done || !regions_total || (cap && !out)) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (limiter >= e->lims.size()) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    SnapScratch sc;
+    int rc = snap_scratch(e, &sc);
+    if (rc != RL_OK) return rc;
+    const uint64_t total = e->lims[limiter].table_bytes / sizeof(Slot) / kRegionSlots;
+    const uint64_t m = snap_clip(region_begin, region_count, total);
+    rc = ensure_img_stage(e, (size_t)std::min<uint64_t>(cap, m * kRegionSlots));
+    if (rc != RL_OK) return rc;
+    rc = snapshot_enqueue(e, limiter, region_begin, region_count, e->img_stage, cap, sc.hdr, sc, nullptr);
+    if (rc != RL_OK) return rc;
+    uint64_t hdr[4] = {0, 0, 0, 0};
+    HIP_OK(hipMemcpyAsync(hdr, sc.hdr, sizeof(hdr), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    if (hdr[0] > cap || hdr[0] > m * kRegionSlots || hdr[1] > m) return RL_E_INTERNAL;
+    *regions_total = hdr[2];
+    *regions_done = hdr[1];
+    if (snap_too_large(m, hdr[1])) {
+        *n_out = (size_t)hdr[3];
+        return RL_E_TOO_LARGE;
+    }
+    if (hdr[0]) HIP_OK(hipMemcpy(out, e->img_stage, (size_t)hdr[0] * sizeof(KeyImage), hipMemcpyDeviceToHost));
+    *n_out = (size_t)hdr[0];
+    return RL_OK;
+}
+
+// The ordered put of n device images on the engine stream, its header into `hdr` (device).
+static int put_enqueue(rl_engine* e, size_t n, const KeyImage* in, uint64_t* hdr, const SnapScratch& sc) {
+    PutArgs a{};
+    a.in = in; a.n = (uint32_t)n; a.n_lim = (uint32_t)e->lims.size(); a.shard_bits = e->shard_bits;
+    a.lims = e->d_lims; a.heads = e->put_heads; a.ctl = sc.ctl; a.hdr = hdr;
+    HIP_OK(launch_put_ordered(a, e->stream));
+    return RL_OK;
+}
+
+extern "C" int rl_put_keys_device(rl_engine* e, size_t n, const rl_key_image* in, uint64_t* hdr,
+                                  void* stream) {
+    if (!e || !hdr || (n && !in) || !aligned16(in)) return RL_E_INVALID_ARG;
+    if ((uint64_t)n > kSnapMaxImages) return RL_E_TOO_LARGE;
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipSetDevice(e->device);
+    SnapScratch sc;
+    int rc = snap_scratch(e, &sc);
+    if (rc == RL_OK) rc = ensure_put_heads(e, n);
+    if (rc != RL_OK) return rc;
+    StreamJoin join(e->stream, (hipStream_t)stream);
+    HIP_OK(join.err);
+    rc = put_enqueue(e, n, (const KeyImage*)in, hdr, sc);
+    if (rc != RL_OK) return rc;
+    HIP_OK(join.finish());
+    return RL_OK;
+}
+
+extern "C" int rl_restore_keys(rl_engine* e, size_t n, const rl_key_image* in, size_t* n_put) {
+    if (!e || (n && !in)) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    for (size_t i = 0; i < n; ++i)
+        if (in[i].limiter >= e->lims.size()) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    const size_t piece = std::min<size_t>(n, (size_t)std::max<uint64_t>(e->opts.max_batch, 1));
+    SnapScratch sc;
+    int rc = snap_scratch(e, &sc);
+    if (rc == RL_OK) rc = ensure_put_heads(e, piece);
+    if (rc == RL_OK) rc = ensure_img_stage(e, piece);
+    if (rc != RL_OK) return rc;
+    size_t failed = 0;
+    for (size_t at = 0; at < n; at += piece) {
+        const size_t m = std::min(piece, n - at);
+        HIP_OK(hipMemcpyAsync(e->img_stage, in + at, m * sizeof(KeyImage), hipMemcpyHostToDevice, e->stream));
+        rc = put_enqueue(e, m, e->img_stage, sc.hdr, sc);
+        if (rc != RL_OK) return rc;
+        uint64_t hdr[4] = {0, 0, 0, 0};
+        HIP_OK(hipMemcpyAsync(hdr, sc.hdr, sizeof(hdr), hipMemcpyDeviceToHost, e->stream));
+        HIP_OK(hipStreamSynchronize(e->stream));
+        if (hdr[2] & ~(uint64_t)kPutRejectOrder) return RL_E_INTERNAL;   // (limiters were checked)
+        if (hdr[2]) {                                 // not in ordered form: nothing was written
+            uint32_t f = 0;
+            rc = put_images_host(e, m, in + at, &f);
+            if (rc != RL_OK) return rc;
+            failed += f;
+        } else {
+            failed += (size_t)hdr[1];
+        }
+    }
+    if (n_put) *n_put = n - failed;
+    return failed ? RL_E_CAPACITY : RL_OK;
 }
 
 extern "C" int rl_sweep_expired(rl_engine* e, int64_t now_ns, uint64_t* reclaimed) {

@@ -361,6 +361,45 @@ struct MoveArgs {
 // drop: every hit's slot becomes a tombstone (key_hash 0 only in a launch of its own)
 hipError_t launch_move_keys(const MoveArgs& a, bool drop, hipStream_t s);
 
+// Whole-table snapshot and ordered put (rl_snapshot.hip; rl_snapshot_keys(_device),
+// rl_put_keys_device, rl_restore_keys). The cut rule and the ordered-form predicate, with the
+// bound on the regions per call: rl_snapshot.hpp. One scratch of fixed size
+// (snap_scratch_bytes: a count and an offset per region of a call, two headers, the put's
+// control words) serves both; the put also needs one u32 per image for its run heads.
+struct PutCtl { uint32_t n_heads, rejected, n_failed, pad; };
+struct SnapScratch {
+    uint32_t* count;               // [kSnapMaxRegions] images per region of the call
+    uint32_t* offset;              // [kSnapMaxRegions] their exclusive scan
+    uint64_t* hdr;                 // [4] the host forms' device-side header
+    PutCtl* ctl;
+};
+size_t snap_scratch_bytes();
+SnapScratch snap_scratch_at(void* base);
+struct SnapArgs {
+    DevLimiter L;
+    uint32_t lim;
+    uint32_t m;                    // regions of this call (<= kSnapMaxRegions, inside the table)
+    uint64_t region_begin, regions_total;
+    uint64_t cap;
+    uint32_t* count;
+    uint32_t* offset;
+    KeyImage* out;                 // [cap], 16-B aligned (nullable with cap 0)
+    uint64_t* hdr;                 // { n_out, regions_done, regions_total, 0 } (rl_engine.h)
+};
+// count, scan (+ header), emit: no host read in between
+hipError_t launch_snapshot(const SnapArgs& a, hipStream_t s);
+struct PutArgs {
+    const KeyImage* in;            // [n], 16-B aligned
+    uint32_t n, n_lim;
+    int shard_bits;
+    const DevLimiter* lims;
+    uint32_t* heads;               // [n] first image of every run of equal destination, any order
+    PutCtl* ctl;
+    uint64_t* hdr;                 // { n_put, n_failed, rejected, n }
+};
+// clear ctl, check (order, limiters, run heads), apply (one wave per run), header
+hipError_t launch_put_ordered(const PutArgs& a, hipStream_t s);
+
 hipError_t launch_export(const Slot* table, uint64_t n_slots, const DevLimiter& L, uint16_t lim,
                          int64_t now_ms, StateRec* out, uint32_t cap, uint32_t* count,
                          hipStream_t s);

@@ -34,11 +34,11 @@ __global__ __launch_bounds__(256) void k_export(const Slot* __restrict__ tab, ui
 
 // Import: one wave per region that receives entries. The region's present slots are
 // staged and rebuilt, then its keys are applied in order: replace the slot holding the
-// key's tag, else claim the first free slot of the key's probe sequence. rl_put_keys runs the
-// same kernel with the images' local-cache words (a.xw); the state import writes 0.
+// key's tag, else claim the first free slot of the key's probe sequence (stage_put,
+// rl_table.hpp). rl_put_keys runs the same kernel with the images' local-cache words (a.xw);
+// the state import writes 0.
 __global__ __launch_bounds__(64) void k_import(ImportArgs a) {
     __shared__ RegionStage S;
-    constexpr uint32_t NS = kRegionSlots;
     const uint32_t g = blockIdx.x, lane = threadIdx.x;
     if (g >= a.n_groups) return;
     Slot* tab = (Slot*)(uintptr_t)a.region_addr[g];
@@ -50,26 +50,8 @@ __global__ __launch_bounds__(64) void k_import(ImportArgs a) {
                  [&](const Slot&) -> RegionStage& { return S; });
     for (uint32_t j = a.group_off[g]; j < a.group_off[g + 1]; ++j) {
         const Slot im = a.img[j];
-        const uint32_t home = slot_home(im.tag);
-        int32_t p = -1;
-        for (uint32_t b = 0; b < NS / 64 && p < 0; ++b) {    // probe order = (b, lane)
-            const uint32_t s = (home + b * 64 + lane) & (NS - 1);
-            const bool used = (S.occ[s] & kOccUsed) != 0;
-            const uint64_t fre = __ballot(!used);
-            const uint64_t hit = __ballot(used && S.tag[s] == im.tag);
-            const uint64_t before = fre ? ((fre & (0 - fre)) - 1) | (fre & (0 - fre)) : ~0ULL;
-            const uint64_t h = hit & before;                  // a hit before the first free slot
-            if (h) p = (int32_t)((home + b * 64 + (uint32_t)__builtin_ctzll(h)) & (NS - 1));
-            else if (fre) p = (int32_t)((home + b * 64 + (uint32_t)__builtin_ctzll(fre)) & (NS - 1));
-        }
-        if (p < 0) {
-            if (lane == 0) atomicAdd(a.fail, 1u);
-        } else if (lane == 0) {
-            S.occ[p] = kOccUsed;
-            S.tag[p] = im.tag; S.sa[p] = im.a; S.sb[p] = im.b; S.sc[p] = im.c;
-            S.sx[p] = a.xw ? a.xw[j] : 0;             // (rl_put_keys carries the cache word)
-        }
-        wave_fence();
+        const uint64_t x = a.xw ? a.xw[j] : 0;        // (rl_put_keys carries the cache word)
+        if (!stage_put(S, im, x, lane) && lane == 0) atomicAdd(a.fail, 1u);
     }
     write_region(S, tab, xt, lane);
 }

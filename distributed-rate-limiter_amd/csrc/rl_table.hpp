@@ -1,7 +1,7 @@
 // rl_table.hpp — how a key is found in a limiter's state table, and what a slot found there
 // means, for the kernels off the decision path: retry-after (rl_retry.hip), key migration
-// (rl_migrate.hip), the census (rl_usage.hip) and export / import / growth / sweep
-// (rl_state.hip). The decision path has its own region load (rl_region.hpp, rl_hot.hpp).
+// (rl_migrate.hip), the census (rl_usage.hip), export / import / growth / sweep
+// (rl_state.hip) and snapshot / ordered put (rl_snapshot.hip). The decision path has its own region load (rl_region.hpp, rl_hot.hpp).
 //
 // Everything here encodes the HBM slot invariant stated above slot_free (rl_device.hpp): a slot
 // is free iff all its words are zero, and a key sits before the first free slot of its probe
@@ -138,6 +138,32 @@ __device__ inline uint32_t stage_region(TabPtr tab, XPtr xt, uint32_t lane, Keep
     }
     wave_fence();
     return dropped;
+}
+
+// One image put into a staged region by the whole wave (state import, rl_put_keys and the
+// ordered put of rl_snapshot.hip): it replaces the slot holding its tag, else claims the first
+// free slot of its probe sequence. False: the region has neither (nothing changes).
+__device__ inline bool stage_put(RegionStage& S, const Slot& im, uint64_t x, uint32_t lane) {
+    constexpr uint32_t NS = kRegionSlots;
+    const uint32_t home = slot_home(im.tag);
+    int32_t p = -1;
+    for (uint32_t b = 0; b < NS / 64 && p < 0; ++b) {    // probe order = (b, lane)
+        const uint32_t s = (home + b * 64 + lane) & (NS - 1);
+        const bool used = (S.occ[s] & kOccUsed) != 0;
+        const uint64_t fre = __ballot(!used);
+        const uint64_t hit = __ballot(used && S.tag[s] == im.tag);
+        const uint64_t before = fre ? ((fre & (0 - fre)) - 1) | (fre & (0 - fre)) : ~0ULL;
+        const uint64_t h = hit & before;                  // a hit before the first free slot
+        if (h) p = (int32_t)((home + b * 64 + (uint32_t)__builtin_ctzll(h)) & (NS - 1));
+        else if (fre) p = (int32_t)((home + b * 64 + (uint32_t)__builtin_ctzll(fre)) & (NS - 1));
+    }
+    if (p >= 0 && lane == 0) {
+        S.occ[p] = kOccUsed;
+        S.tag[p] = im.tag; S.sa[p] = im.a; S.sb[p] = im.b; S.sc[p] = im.c;
+        S.sx[p] = x;
+    }
+    wave_fence();
+    return p >= 0;
 }
 
 template <class TabPtr, class XPtr>

@@ -1,6 +1,7 @@
 // ratelimiter.cpp — see ratelimiter.hpp.
 #include "ratelimiter.hpp"
 
+#include <algorithm>
 #include <cstring>
 
 namespace ratelimiter {
@@ -122,6 +123,41 @@ std::vector<std::pair<uint64_t, int64_t>> GpuEngine::topConsumers(uint16_t limit
     std::vector<std::pair<uint64_t, int64_t>> out(nOut);
     for (size_t i = 0; i < nOut; ++i) out[i] = {key[i], used[i]};
     return out;
+}
+
+size_t GpuEngine::snapshot(uint16_t limiter, size_t chunkImages, const SnapshotSink& sink) {
+    const size_t cap = std::max<size_t>(chunkImages, RL_SNAPSHOT_MIN_CAP);
+    std::vector<rl_key_image> buf(cap);
+    std::lock_guard<std::mutex> lk(mu_);             // no batch of this object between the chunks
+    size_t delivered = 0;
+    uint64_t at = 0, total0 = 0;
+    for (bool first = true;; first = false) {
+        size_t n = 0;
+        uint64_t done = 0, total = 0;
+        const int st = rl_snapshot_keys(e_, limiter, at, ~0ULL, buf.data(), cap, &n, &done, &total);
+        if (st == RL_E_INVALID_ARG) throw IllegalArgumentException(std::string("snapshot: ") + rl_strerror(st));
+        if (st != RL_OK) throw StorageException(std::string("snapshot: ") + rl_strerror(st), st);
+        if (!first && total != total0)
+            throw StorageException("snapshot: the table grew between two chunks", RL_E_INTERNAL);
+        total0 = total;
+        if (n && sink) sink(buf.data(), n);
+        delivered += n;
+        at += done;
+        if (at >= total) return delivered;
+    }
+}
+
+size_t GpuEngine::restore(const rl_key_image* images, size_t n) {
+    if (n && !images) throw IllegalArgumentException("restore: null images");
+    size_t put = 0;
+    int st;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        st = rl_restore_keys(e_, n, images, &put);
+    }
+    if (st == RL_E_INVALID_ARG) throw IllegalArgumentException(std::string("restore: ") + rl_strerror(st));
+    if (st != RL_OK) throw StorageException(std::string("restore: ") + rl_strerror(st), st);
+    return put;
 }
 
 GpuRateLimiter::GpuRateLimiter(std::shared_ptr<GpuEngine> engine, Algorithm algo,

@@ -138,6 +138,19 @@ class GpuEngine {
     // IllegalArgumentException for k == 0, k > RL_TOP_KEYS_MAX, minUsed < 0.
     std::vector<std::pair<uint64_t, int64_t>> topConsumers(uint16_t limiter, int64_t nowNanos, uint32_t k,
                                                            int64_t minUsed, uint64_t* nMatch = nullptr);
+    // rl_snapshot_keys over a limiter's whole table: `sink` receives the images chunk by chunk (at
+    // most chunkImages each, at least RL_SNAPSHOT_MIN_CAP), in (region, slot) order; the chunks
+    // together are a point-in-time checkpoint if no batch runs on this engine meanwhile (the engine
+    // is held for the whole call, so none of this object's does). Returns the images delivered.
+    // Read-only. IllegalArgumentException for an unknown limiter, StorageException if the table
+    // grew between two chunks (RL_E_INTERNAL) or on a device error.
+    using SnapshotSink = std::function<void(const rl_key_image*, size_t)>;
+    size_t snapshot(uint16_t limiter, size_t chunkImages, const SnapshotSink& sink);
+    // rl_restore_keys: puts images (a snapshot's chunks in order take the device's ordered path,
+    // anything else the path of rl_put_keys) into this engine's tables as they are sized; size a
+    // fresh engine's limiter first (RateLimitConfig.expectedKeys, or rl_grow_limiter). Returns the
+    // images put; StorageException with RL_E_CAPACITY if a region had no free slot.
+    size_t restore(const rl_key_image* images, size_t n);
 
   private:
     rl_engine* e_ = nullptr;

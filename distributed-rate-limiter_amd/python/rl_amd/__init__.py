@@ -34,6 +34,8 @@ RETRY_NEVER, RETRY_INVALID = -1, -2   # RL_RETRY_* (rl_retry_after)
 TOP_KEYS_MAX, TOP_KEYS_CANDIDATES = 4096, 65536   # RL_TOP_KEYS_* (rl_top_keys)
 USAGE_BINS, USAGE_CANDIDATES = 16, 65536   # RL_USAGE_* (rl_limiter_usage, rl_top_consumers)
 MOVE_KEYS_MAX = 8192                       # RL_MOVE_KEYS_MAX: keys per rl_copy_keys / rl_drop_keys
+SNAPSHOT_MIN_CAP = 256                     # RL_SNAPSHOT_MIN_CAP: a snapshot cap that always makes progress
+PUT_REJECT_ORDER, PUT_REJECT_LIMITER = 1, 2   # `rejected` bits of rl_put_keys_device's header
 OPT_STAGE_TIMING = 1
 OPT_PIPELINE = 2       # RL_OPT_PIPELINE: partition of batch k+1 overlaps batch k's decisions
 OPT_FIXED_CAPACITY = 4  # RL_OPT_FIXED_CAPACITY: no on-demand table growth
@@ -59,6 +61,7 @@ EXPORTS = [
     "rl_limiter_usage", "rl_top_consumers",
     "rl_copy_keys", "rl_drop_keys", "rl_put_keys",
     "rl_router_replan_directory", "rl_router_replan_directory_sampled",
+    "rl_snapshot_keys", "rl_snapshot_keys_device", "rl_put_keys_device", "rl_restore_keys",
 ]
 RCCL_EXPORTS = ["rl_rccl_unique_id", "rl_transport_rccl_create", "rl_transport_rccl_destroy"]
 STATE_SW_BUCKET, STATE_TB_BUCKET = 0, 1
@@ -220,6 +223,12 @@ def lib():
     L.rl_router_replan_directory_sampled.argtypes = [vp, sz, vp, u32, ctypes.c_uint64,
                                                      ctypes.POINTER(u32),
                                                      ctypes.POINTER(ctypes.c_uint64), vp]
+    L.rl_snapshot_keys.argtypes = [vp, u16, ctypes.c_uint64, ctypes.c_uint64, vp, sz,
+                                   ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_uint64),
+                                   ctypes.POINTER(ctypes.c_uint64)]
+    L.rl_snapshot_keys_device.argtypes = [vp, u16, ctypes.c_uint64, ctypes.c_uint64, vp, sz, vp, vp]
+    L.rl_put_keys_device.argtypes = [vp, sz, vp, vp, vp]
+    L.rl_restore_keys.argtypes = [vp, sz, vp, ctypes.POINTER(sz)]
     _lib = L
     return L
 
@@ -543,6 +552,72 @@ class Engine:
                                  ctypes.byref(n))
         if st not in (RL_OK, RL_E_CAPACITY):
             raise RlError(st, "rl_put_keys")
+        return st, n.value
+
+    def snapshot_keys(self, limiter, region_begin, region_count, cap, out=None):
+        """One chunk of a limiter's table as images (rl_snapshot_keys): the regions
+        [region_begin, region_begin + region_count), whole regions only, in (region, slot) order.
+        Returns (images, status, n_out, regions_done, regions_total): `images` is the buffer of
+        `cap` entries (`out`, or a zeroed KEY_IMAGE_DTYPE array) of which the first n_out are
+        written; status is RL_OK or RL_E_TOO_LARGE (n_out = the first region's count), anything
+        else raises. Read-only."""
+        cap = int(cap)
+        if out is None:
+            out = np.zeros(cap, KEY_IMAGE_DTYPE)
+        assert out.dtype == KEY_IMAGE_DTYPE and out.shape[0] >= cap
+        n, done, total = ctypes.c_size_t(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        st = self._L.rl_snapshot_keys(self._h, int(limiter), int(region_begin), int(region_count),
+                                      _p(out) if cap else None, cap, ctypes.byref(n),
+                                      ctypes.byref(done), ctypes.byref(total))
+        if st not in (RL_OK, RL_E_TOO_LARGE):
+            raise RlError(st, "rl_snapshot_keys")
+        return out, st, n.value, done.value, total.value
+
+    def snapshot(self, limiter, chunk=1 << 20):
+        """Generator over a limiter's whole table in chunks of at most `chunk` images (at least
+        SNAPSHOT_MIN_CAP): yields KEY_IMAGE_DTYPE arrays whose concatenation is the table in
+        (region, slot) order. No batch may run between the chunks of a point-in-time snapshot;
+        raises RuntimeError if the table grew meanwhile."""
+        chunk = max(int(chunk), SNAPSHOT_MIN_CAP)
+        at, total0 = 0, None
+        while True:
+            out, st, n, done, total = self.snapshot_keys(limiter, at, 1 << 62, chunk)
+            if st != RL_OK:
+                raise RlError(st, "rl_snapshot_keys")
+            if total0 is not None and total != total0:
+                raise RuntimeError("the table grew between two snapshot chunks: start over")
+            total0 = total
+            if n:
+                yield out[:n]
+            at += done
+            if at >= total:
+                return
+
+    def snapshot_keys_device(self, limiter, region_begin, region_count, out, cap, hdr, stream=None):
+        """rl_snapshot_keys_device: `out` (48-byte images) and `hdr` (4 x 8 bytes) are device
+        buffers (torch tensors or raw pointers); asynchronous, hdr = {n_out, regions_done,
+        regions_total, 0}."""
+        st = self._L.rl_snapshot_keys_device(self._h, int(limiter), int(region_begin),
+                                             int(region_count), _p(out), int(cap), _p(hdr), _p(stream))
+        if st != RL_OK:
+            raise RlError(st, "rl_snapshot_keys_device")
+
+    def put_keys_device(self, n, images, hdr, stream=None):
+        """rl_put_keys_device: n device images in ordered form (a snapshot's order); asynchronous,
+        hdr (device, 4 x 8 bytes) = {n_put, n_failed, rejected, n}."""
+        st = self._L.rl_put_keys_device(self._h, int(n), _p(images), _p(hdr), _p(stream))
+        if st != RL_OK:
+            raise RlError(st, "rl_put_keys_device")
+
+    def restore_keys(self, images):
+        """Insert host KEY_IMAGE_DTYPE images of any order and number (rl_restore_keys). Returns
+        (status, images put) as put_keys does."""
+        images = np.ascontiguousarray(images, KEY_IMAGE_DTYPE)
+        n = ctypes.c_size_t(0)
+        st = self._L.rl_restore_keys(self._h, images.shape[0], _p(images) if images.shape[0] else None,
+                                     ctypes.byref(n))
+        if st not in (RL_OK, RL_E_CAPACITY):
+            raise RlError(st, "rl_restore_keys")
         return st, n.value
 
     def sweep_expired(self, now_ns) -> int:

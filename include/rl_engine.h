@@ -395,6 +395,76 @@ int  rl_drop_keys(rl_engine* e, size_t n, const uint64_t* key_hash, uint64_t* n_
  * had no free slot; the other images are put. *n_put (nullable) = images put. */
 int  rl_put_keys(rl_engine* e, size_t n, const rl_key_image* in, size_t* n_put);
 
+/* ---- snapshot / restore: a whole table as images ------------------------------------
+ * rl_copy_keys needs the keys and takes RL_MOVE_KEYS_MAX of them; rl_export_state loses the
+ * local-cache word, costs one atomic per slot and sorts on the host. These four move a whole
+ * limiter's table as rl_key_image arrays with no sort anywhere (checkpoint an engine, warm a
+ * replica, rebuild an engine after a device reset): an engine restored from a snapshot decides
+ * every later request exactly as the snapshotted one would have.
+ * A key's region is the region_bits bits of mix64(key_hash) below the shard bits, so for a table
+ * with fewer region bits k' <= k, region_k' = region_k >> (k - k'): images in the region order of
+ * the source are already grouped by region for any destination with the same shard count and at
+ * most as many regions. The snapshot emits that order; the device put relies on it.
+ * Common rules, as for the census and migration calls. The host forms (rl_snapshot_keys,
+ * rl_restore_keys) run on the engine's stream behind every batch submitted before them
+ * (RL_OPT_PIPELINE included) and synchronise; the device forms are enqueued behind those batches
+ * and return. All four work on the table as installed: a growth the last batch asked for but
+ * nobody has collected is not applied, and a put never grows a table (size a fresh destination
+ * first with rl_grow_limiter(limiter, regions_total * 128)). The snapshot calls only read: no
+ * state, cache word, batch statistic, and not the status rl_last_status reports. None of the four
+ * collects that status. RL_E_INVALID_ARG, before any device call and with every output untouched:
+ * a null engine (checked first), an unknown limiter (snapshot), a null output or header pointer,
+ * cap > 0 with a null out, n > 0 with a null in, a device image array that is not 16-byte aligned
+ * (every element of a hipMalloc'ed rl_key_image array is). One snapshot or put may be in flight
+ * per engine. Device memory, allocated by the first call and freed by rl_destroy: 8 B per region
+ * of a call + 48 B = 512 KiB (a call handles at most 65536 regions, whatever the table's size);
+ * 4 B per image of the largest put so far; the host forms' staged images (min(cap, 256 x the
+ * regions of the call), or min(n, rl_opts.max_batch), x 48 B).
+ * Consistency: a chunk shows the table as it was when the chunk ran. A point-in-time snapshot
+ * needs no batch between its chunks; a caller that sees regions_total change between two chunks
+ * (the table grew) starts over. */
+#define RL_SNAPSHOT_MIN_CAP 256   /* = slots per region: a cap that always makes progress */
+
+/* Images of every slot of `limiter` that holds state or a cache word (the rule of rl_copy_keys:
+ * tombstones and free slots give none; no `now`, dead-by-TTL state travels as it is), for the
+ * regions [region_begin, region_begin + region_count) clipped to the table, in
+ * (region ascending, slot index ascending) order. Whole regions only:
+ *   regions_done  = R, the number of leading regions of the range whose images were all written
+ *   n_out         = images written = sum of those R regions' counts (<= cap)
+ *   regions_total = the limiter's region count when the call ran (rl_limiter_slots / 256)
+ * R is the largest prefix of the range's first 65536 regions that fits cap (cap itself counts up
+ * to 2^31). R >= 1 whenever cap >= RL_SNAPSHOT_MIN_CAP and the clipped range is not empty; the
+ * next chunk starts at region_begin + R.
+ * Entries at and beyond n_out are untouched. If even the first region does not fit (only possible
+ * with cap < 256): RL_E_TOO_LARGE, regions_done = 0, *n_out = that region's count, nothing written.
+ * region_begin >= regions_total: RL_OK with 0 / 0. `out` is a HOST buffer. */
+int  rl_snapshot_keys(rl_engine* e, uint16_t limiter, uint64_t region_begin, uint64_t region_count,
+                      rl_key_image* out, size_t cap, size_t* n_out, uint64_t* regions_done,
+                      uint64_t* regions_total);
+/* DEVICE out[cap] and hdr[4] = { n_out, regions_done, regions_total, 0 }; enqueued on `stream`
+ * (NULL = the engine's) with no host synchronisation; returns argument / launch status only.
+ * The too-large case reads { 0, 0, regions_total, first region's count }. */
+int  rl_snapshot_keys_device(rl_engine* e, uint16_t limiter, uint64_t region_begin,
+                             uint64_t region_count, rl_key_image* out, size_t cap, uint64_t* hdr,
+                             void* stream);
+
+/* rl_put_keys on DEVICE images with no per-image host work: same effect on the table. Each image
+ * replaces the key's state and cache word in the region it hashes to; there is no ownership check.
+ * Requires ORDERED FORM: (limiter, destination region) non-decreasing over in[0..n).
+ * rl_snapshot_keys output has it for a destination whose limiter has the same shard_bits and at
+ * most as many regions (chunks of several limiters: in limiter order). Duplicate keys are applied
+ * in array order.
+ * hdr[4] = { n_put, n_failed, rejected, n }: n_failed = images that found no free slot
+ * (the others are put). rejected bit 0 = not in ordered form, bit 1 = an image names a limiter
+ * the engine does not have; if rejected != 0 the table is untouched and n_put = 0.
+ * RL_E_TOO_LARGE: n > 2^31. */
+int  rl_put_keys_device(rl_engine* e, size_t n, const rl_key_image* in, uint64_t* hdr, void* stream);
+
+/* HOST images of any order and any size. Staged to the device in pieces of at most
+ * rl_opts.max_batch images. Each piece goes through rl_put_keys_device. A piece that is not in
+ * ordered form takes the path of rl_put_keys. Same result and status as rl_put_keys(n, in). */
+int  rl_restore_keys(rl_engine* e, size_t n, const rl_key_image* in, size_t* n_put);
+
 /* Background TTL sweep (Redis active expiry of the PEXPIRE deadlines set at
  * RedisRateLimitStorage.java:41-44 and Lua :64): frees every slot none of whose buckets is live at
  * now_ns, so table memory tracks live keys even for regions no batch touches. (Batches already
