@@ -18,6 +18,7 @@
 
 #include "../../include/rl_engine.h"
 #include "rl_launch.hpp"
+#include "rl_shrink.hpp"
 #include "rl_snapshot.hpp"
 
 using namespace rl;
@@ -2430,4 +2431,129 @@ extern "C" int rl_sweep_expired(rl_engine* e, int64_t now_ns, uint64_t* reclaime
     if (reclaimed)
         for (uint32_t c : h) *reclaimed += c;
     return RL_OK;
+}
+
+// ---------------------------------------------------------------- table shrink
+// rl_shrink.hip on the engine stream; the rules in rl_shrink.hpp. The plan reads the table as
+// installed, as the census does (no collect_status; no limiter state, batch scratch, d_stats,
+// d_ctl or status word is touched). Its scratch (12 B per region + the control block) lives for
+// the call only.
+static_assert(RL_SHRINK_FILL_MAX == kShrinkFillMax && RL_SHRINK_LEVELS == kShrinkLevels, "shrink constants");
+static_assert(2 * RL_SHRINK_FILL_MAX == kGrowUsed, "a shrunk region doubles its keys before it flags growth");
+static_assert(sizeof(rl_shrink_report) == 8 * 5 + 4 * RL_SHRINK_LEVELS, "rl_shrink_report layout");
+
+// (e->mu held) The plan of limiter li at now_ms into *rep; synchronises e->stream.
+static int shrink_plan_locked(rl_engine* e, size_t li, int64_t now_ms, uint64_t min_keys,
+                              rl_shrink_report* rep) {
+    const HostLimiter& h = e->lims[li];
+    const int k = h.dev.region_bits;
+    const uint64_t n_regions = 1ULL << k;
+    const uint32_t levels = shrink_levels(k);
+    DevBuf<unsigned char> buf;
+    if (buf.alloc(shrink_scratch_bytes(n_regions)) != RL_OK) return RL_E_NOMEM;
+    const ShrinkScratch sc = shrink_scratch_at(buf, n_regions);
+    ShrinkCtl c;
+    HIP_OK(launch_shrink_plan(sc, h.dev, n_regions, levels, now_ms, e->stream));
+    HIP_OK(hipMemcpyAsync(&c, sc.ctl, sizeof(c), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    rl_shrink_report r{};
+    r.slots_before = h.table_bytes / sizeof(Slot);
+    r.used_before = c.used;
+    r.kept = c.kept;
+    r.levels = levels;
+    for (uint32_t i = 0; i < levels; ++i) r.fullest[i] = c.fullest[i];
+    r.halvings = shrink_halvings(r.fullest, levels, r.slots_before, min_keys, e->opts.shard_count);
+    r.slots_after = r.slots_before >> r.halvings;
+    *rep = r;
+    return RL_OK;
+}
+
+extern "C" int rl_shrink_plan(rl_engine* e, uint16_t limiter, int64_t now_ns, uint64_t min_keys,
+                              rl_shrink_report* out) {
+    if (!e || !out) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (limiter >= e->lims.size()) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    rl_shrink_report r;
+    const int rc = shrink_plan_locked(e, limiter, floor_div_ms(now_ns), min_keys, &r);
+    if (rc == RL_OK) *out = r;
+    return rc;
+}
+
+// Halve limiter li's region count j times: ceil(j / 3) merge passes (k_shrink_merge) through
+// fresh tables, the keep rule of the sweep in the first one; the old table is freed and the
+// limiter record changed only after the last pass has succeeded and placed every slot. Then,
+// as grow_once: region ids of the later limiters shifted, the route lists cleared.
+static int shrink_by(rl_engine* e, size_t li, uint32_t j, int64_t now_ms) {
+    HostLimiter& h = e->lims[li];
+    DevLimiter& d = h.dev;
+    const int k = d.region_bits;
+    if (j == 0 || (int)j > k - kBinShift) return RL_E_INTERNAL;
+    struct Tab { void* t = nullptr; void* x = nullptr; };
+    std::vector<Tab> tabs(shrink_passes(j));
+    DevBuf<uint32_t> fail;
+    auto drop = [&] { for (Tab& t : tabs) { dfree(t.t); dfree(t.x); } };
+    int rc = fail.alloc(1);
+    int bits = k;
+    for (uint32_t p = 0; p < tabs.size() && rc == RL_OK; ++p) {
+        bits -= (int)shrink_pass_bits(j, p);
+        const size_t slots = (size_t)(1ULL << bits) * kRegionSlots;
+        rc = dalloc(&tabs[p].t, slots * sizeof(Slot));
+        if (rc == RL_OK && h.cache_table) rc = dalloc(&tabs[p].x, slots * sizeof(uint64_t));
+    }
+    if (rc != RL_OK) { drop(); return rc; }
+    hipError_t he = hipMemsetAsync(fail, 0, sizeof(uint32_t), e->stream);
+    const void* src_t = h.table;
+    const void* src_x = h.cache_table;
+    bits = k;
+    for (uint32_t p = 0; p < tabs.size() && he == hipSuccess; ++p) {
+        const uint32_t s = shrink_pass_bits(j, p);
+        bits -= (int)s;
+        he = launch_shrink_merge((const Slot*)src_t, (const uint64_t*)src_x, (Slot*)tabs[p].t,
+                                 (uint64_t*)tabs[p].x, 1ULL << bits, s, d, now_ms, p == 0, fail, e->stream);
+        src_t = tabs[p].t;
+        src_x = tabs[p].x;
+    }
+    uint32_t failed = 0;
+    if (he == hipSuccess) he = hipMemcpyAsync(&failed, fail, sizeof(failed), hipMemcpyDeviceToHost, e->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+    if (he != hipSuccess) {
+        std::fprintf(stderr, "rl_engine: table shrink failed: %s\n", hipGetErrorString(he));
+        (void)hipStreamSynchronize(e->stream);       // nothing may still write the tables freed here
+        drop();
+        return RL_E_DEVICE;
+    }
+    if (failed) { drop(); return RL_E_INTERNAL; }    // (the plan excludes it; the old table stands)
+    Tab last = tabs.back();
+    tabs.pop_back();
+    drop();                                          // the intermediate tables
+    dfree(h.table); dfree(h.cache_table);
+    h.table = last.t; h.cache_table = last.x;
+    h.table_bytes = (size_t)(1ULL << bits) * kRegionSlots * sizeof(Slot);
+    d.table = (uint64_t)(uintptr_t)last.t;
+    d.cache_table = (uint64_t)(uintptr_t)last.x;
+    d.region_bits = bits;
+    uint32_t base = 0;
+    for (auto& l : e->lims) { l.dev.region_base = base; base += 1u << l.dev.region_bits; }
+    e->n_regions = base;
+    // region ids changed: the next batch routes nothing (its hot preparation lists anew)
+    HIP_OK(hipMemset(e->route_list, 0xFF, 2 * kRouteWords * sizeof(uint32_t)));
+    return upload_limiters(e);
+}
+
+extern "C" int rl_shrink_limiter(rl_engine* e, uint16_t limiter, int64_t now_ns, uint64_t min_keys,
+                                 rl_shrink_report* out) {
+    if (!e) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);           // held across plan and merge: the plan's proof stands
+    if (limiter >= e->lims.size()) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    HIP_OK(hipStreamSynchronize(e->stream));         // nothing in flight, as for grow_once
+    if (e->pstream) HIP_OK(hipStreamSynchronize(e->pstream));
+    const int64_t now = floor_div_ms(now_ns);
+    rl_shrink_report r;
+    int rc = shrink_plan_locked(e, limiter, now, min_keys, &r);
+    if (rc != RL_OK) return rc;
+    if (r.halvings) rc = shrink_by(e, limiter, r.halvings, now);
+    if (rc == RL_OK && out) *out = r;
+    return rc;
 }

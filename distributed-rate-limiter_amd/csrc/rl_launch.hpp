@@ -409,6 +409,31 @@ hipError_t launch_grow(const Slot* old_tab, const uint64_t* old_x, Slot* new_tab
 hipError_t launch_sweep(const DevLimiter& L, uint64_t n_slots, int64_t now_ms, uint32_t* count,
                         hipStream_t s);                     // (L's own tables, n_slots of them)
 
+// Table shrink (rl_shrink.hip; rl_shrink_plan / rl_shrink_limiter; the rules: rl_shrink.hpp).
+// The plan: per-region counts of the slots live at `now` and of the used slots, their totals,
+// and the largest live count of a region at every level of pairwise merging. The merge: one
+// wave per destination region stages the kept slots of its 2^s source regions and writes the
+// region whole (the inverse of k_grow).
+struct ShrinkCtl {
+    unsigned long long kept, used; // slots live at now / not free, over the table
+    uint32_t fullest[24];          // [kShrinkLevels]
+    uint32_t fail;                 // kept slots that found no free slot in a merge's stage
+    uint32_t pad;
+};
+// scratch: ctl, then kept[n], used[n] and the levels' sums (< n words) for n regions
+size_t shrink_scratch_bytes(uint64_t n_regions);
+struct ShrinkScratch { ShrinkCtl* ctl; uint32_t* kept; uint32_t* used; uint32_t* sums; };
+ShrinkScratch shrink_scratch_at(void* base, uint64_t n_regions);
+// clears ctl, counts, reduces `levels` levels (levels - 1 pairwise folds); L's own tables
+hipError_t launch_shrink_plan(const ShrinkScratch& sc, const DevLimiter& L, uint64_t n_regions,
+                              uint32_t levels, int64_t now_ms, hipStream_t s);
+// n_dst destination regions of 2^s (s <= 3) source regions each. live_only: keep the slots
+// live at now_ms (slot_live, the first pass); else every slot that holds state. L gives the
+// limiter's parameters only: the tables are the four pointers. *fail += slots not placed.
+hipError_t launch_shrink_merge(const Slot* src_tab, const uint64_t* src_x, Slot* dst_tab,
+                               uint64_t* dst_x, uint64_t n_dst, uint32_t s, const DevLimiter& L,
+                               int64_t now_ms, bool live_only, uint32_t* fail, hipStream_t st);
+
 hipError_t launch_upsweep(const PartArgs& a, bool raw, bool wide, hipStream_t s);
 hipError_t launch_scatter(const PartArgs& a, bool raw, bool wide, hipStream_t s);
 hipError_t launch_scan_rows(const uint32_t* in, uint32_t* out, uint32_t rows, uint32_t cols,

@@ -1,7 +1,8 @@
 // rl_table.hpp — how a key is found in a limiter's state table, and what a slot found there
 // means, for the kernels off the decision path: retry-after (rl_retry.hip), key migration
 // (rl_migrate.hip), the census (rl_usage.hip), export / import / growth / sweep
-// (rl_state.hip) and snapshot / ordered put (rl_snapshot.hip). The decision path has its own region load (rl_region.hpp, rl_hot.hpp).
+// (rl_state.hip), snapshot / ordered put (rl_snapshot.hip) and the table shrink
+// (rl_shrink.hip). The decision path has its own region load (rl_region.hpp, rl_hot.hpp).
 //
 // Everything here encodes the HBM slot invariant stated above slot_free (rl_device.hpp): a slot
 // is free iff all its words are zero, and a key sits before the first free slot of its probe
@@ -138,6 +139,22 @@ __device__ inline uint32_t stage_region(TabPtr tab, XPtr xt, uint32_t lane, Keep
     }
     wave_fence();
     return dropped;
+}
+
+// One slot inserted by one lane as stage_region's loop does, but giving up after a whole turn
+// of the region: for a stage fed from several source regions (the table shrink's merge,
+// rl_shrink.hip), where "the kept slots fit" is the caller's plan and not a property of one
+// region. False: no free LDS slot in kRegionSlots steps (nothing was written).
+__device__ inline bool stage_insert_bounded(RegionStage& S, const Slot& v, uint64_t x) {
+    constexpr uint32_t NS = kRegionSlots;
+    uint32_t p = slot_home(v.tag);
+    for (uint32_t step = 0; step < NS; ++step, p = (p + 1) & (NS - 1)) {
+        if (atomicCAS(&S.occ[p], 0u, 1u) != 0u) continue;
+        S.tag[p] = v.tag; S.sa[p] = v.a; S.sb[p] = v.b; S.sc[p] = v.c;
+        S.sx[p] = x;
+        return true;
+    }
+    return false;
 }
 
 // One image put into a staged region by the whole wave (state import, rl_put_keys and the

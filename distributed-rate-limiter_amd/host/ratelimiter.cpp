@@ -160,6 +160,18 @@ size_t GpuEngine::restore(const rl_key_image* images, size_t n) {
     return put;
 }
 
+rl_shrink_report GpuEngine::shrink(uint16_t limiter, int64_t nowNanos, uint64_t minKeys) {
+    rl_shrink_report r{};
+    int st;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        st = rl_shrink_limiter(e_, limiter, nowNanos, minKeys, &r);
+    }
+    if (st == RL_E_INVALID_ARG) throw IllegalArgumentException(std::string("shrink: ") + rl_strerror(st));
+    if (st != RL_OK) throw StorageException(std::string("shrink: ") + rl_strerror(st), st);
+    return r;
+}
+
 GpuRateLimiter::GpuRateLimiter(std::shared_ptr<GpuEngine> engine, Algorithm algo,
                                const RateLimitConfig& cfg, Clock clock, int batchWindowMicros)
     : allowedRequests(algo == Algorithm::TokenBucket ? "ratelimiter.tokenbucket.allowed"
@@ -326,6 +338,19 @@ rl_usage GpuRateLimiter::usage() {
         ~Release() { lk.lock(); self->flushing_ = false; self->cv_.notify_all(); }
     } rel{this, lk};
     return engine_->usage(id_, now);
+}
+
+rl_shrink_report GpuRateLimiter::compact() {
+    std::unique_lock<std::mutex> lk(mu_);
+    cv_.wait(lk, [&] { return !flushing_; });
+    flushing_ = true;
+    const int64_t now = clock_();
+    lk.unlock();
+    struct Release {
+        GpuRateLimiter* self; std::unique_lock<std::mutex>& lk;
+        ~Release() { lk.lock(); self->flushing_ = false; self->cv_.notify_all(); }
+    } rel{this, lk};
+    return engine_->shrink(id_, now, cfg_.expectedKeys);
 }
 
 std::vector<std::pair<uint64_t, int64_t>> GpuRateLimiter::topConsumers(uint32_t k, int64_t minUsed) {

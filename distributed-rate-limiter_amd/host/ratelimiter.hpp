@@ -151,6 +151,12 @@ class GpuEngine {
     // fresh engine's limiter first (RateLimitConfig.expectedKeys, or rl_grow_limiter). Returns the
     // images put; StorageException with RL_E_CAPACITY if a region had no free slot.
     size_t restore(const rl_key_image* images, size_t n);
+    // rl_shrink_limiter: halves the limiter's region count as often as its keys live at nowNanos
+    // allow (room for minKeys keys is kept), dropping dead slots on the way; returns the plan acted
+    // on (halvings == 0: the table was left alone). Decisions are unchanged. nowNanos must not
+    // exceed the now of any later request. IllegalArgumentException for an unknown limiter,
+    // StorageException on a device error (the old table then still stands).
+    rl_shrink_report shrink(uint16_t limiter, int64_t nowNanos, uint64_t minKeys = 0);
 
   private:
     rl_engine* e_ = nullptr;
@@ -193,6 +199,11 @@ class GpuRateLimiter : public RateLimiter {
     // (keyHash(key), used) pairs (the candidates for reset(key) or an abuse report). Exact.
     // Throws IllegalArgumentException for k == 0, k > RL_TOP_KEYS_MAX, minUsed < 0.
     std::vector<std::pair<uint64_t, int64_t>> topConsumers(uint32_t k, int64_t minUsed = 1);
+    // Gives this limiter's table memory back after a flood of keys has expired (Redis frees
+    // memory as keys expire): shrinks its own table at the clock's now, as usage() reads it, and
+    // keeps room for config().expectedKeys. Sees every tryAcquire of this object that has
+    // returned; later decisions are unchanged.
+    rl_shrink_report compact();
     // the reference's permits check (SlidingWindowRateLimiter.java:87-89,
     // TokenBucketRateLimiter.java:106-108): throws IllegalArgumentException for permits <= 0
     static void requirePositive(int permits);

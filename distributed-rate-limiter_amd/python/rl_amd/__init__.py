@@ -35,6 +35,7 @@ TOP_KEYS_MAX, TOP_KEYS_CANDIDATES = 4096, 65536   # RL_TOP_KEYS_* (rl_top_keys)
 USAGE_BINS, USAGE_CANDIDATES = 16, 65536   # RL_USAGE_* (rl_limiter_usage, rl_top_consumers)
 MOVE_KEYS_MAX = 8192                       # RL_MOVE_KEYS_MAX: keys per rl_copy_keys / rl_drop_keys
 SNAPSHOT_MIN_CAP = 256                     # RL_SNAPSHOT_MIN_CAP: a snapshot cap that always makes progress
+SHRINK_FILL_MAX, SHRINK_LEVELS = 104, 24   # RL_SHRINK_* (rl_shrink_plan, rl_shrink_limiter)
 PUT_REJECT_ORDER, PUT_REJECT_LIMITER = 1, 2   # `rejected` bits of rl_put_keys_device's header
 OPT_STAGE_TIMING = 1
 OPT_PIPELINE = 2       # RL_OPT_PIPELINE: partition of batch k+1 overlaps batch k's decisions
@@ -62,6 +63,7 @@ EXPORTS = [
     "rl_copy_keys", "rl_drop_keys", "rl_put_keys",
     "rl_router_replan_directory", "rl_router_replan_directory_sampled",
     "rl_snapshot_keys", "rl_snapshot_keys_device", "rl_put_keys_device", "rl_restore_keys",
+    "rl_shrink_plan", "rl_shrink_limiter",
 ]
 RCCL_EXPORTS = ["rl_rccl_unique_id", "rl_transport_rccl_create", "rl_transport_rccl_destroy"]
 STATE_SW_BUCKET, STATE_TB_BUCKET = 0, 1
@@ -108,6 +110,13 @@ class Usage(ctypes.Structure):
                                                  "exhausted_keys", "cache_blocked",
                                                  "used_permits")] + \
                [("hist", ctypes.c_uint64 * USAGE_BINS)]
+
+
+class ShrinkReport(ctypes.Structure):
+    """rl_shrink_report (include/rl_engine.h): the plan of a table shrink."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("slots_before", "slots_after", "used_before", "kept")] + \
+               [("halvings", ctypes.c_uint32), ("levels", ctypes.c_uint32),
+                ("fullest", ctypes.c_uint32 * SHRINK_LEVELS)]
 
 
 class KeyImage(ctypes.Structure):
@@ -229,6 +238,8 @@ def lib():
     L.rl_snapshot_keys_device.argtypes = [vp, u16, ctypes.c_uint64, ctypes.c_uint64, vp, sz, vp, vp]
     L.rl_put_keys_device.argtypes = [vp, sz, vp, vp, vp]
     L.rl_restore_keys.argtypes = [vp, sz, vp, ctypes.POINTER(sz)]
+    L.rl_shrink_plan.argtypes = [vp, u16, i64, ctypes.c_uint64, ctypes.POINTER(ShrinkReport)]
+    L.rl_shrink_limiter.argtypes = [vp, u16, i64, ctypes.c_uint64, ctypes.POINTER(ShrinkReport)]
     _lib = L
     return L
 
@@ -627,6 +638,31 @@ class Engine:
         if st != RL_OK:
             raise RlError(st, "rl_sweep_expired")
         return n.value
+
+    @staticmethod
+    def _shrink_dict(r) -> dict:
+        d = {f: getattr(r, f) for f, _ in ShrinkReport._fields_ if f != "fullest"}
+        d["fullest"] = list(r.fullest)[:r.levels]
+        return d
+
+    def shrink_plan(self, limiter, now_ns, min_keys=0) -> dict:
+        """What shrink_limiter would do at now_ns (rl_shrink_plan): a dict of the rl_shrink_report
+        fields, `fullest` as a list of `levels` counts. Read-only."""
+        r = ShrinkReport()
+        st = self._L.rl_shrink_plan(self._h, int(limiter), int(now_ns), int(min_keys), ctypes.byref(r))
+        if st != RL_OK:
+            raise RlError(st, "rl_shrink_plan")
+        return self._shrink_dict(r)
+
+    def shrink_limiter(self, limiter, now_ns, min_keys=0) -> dict:
+        """Halve the limiter's region count as often as its live keys at now_ns allow
+        (rl_shrink_limiter), keeping room for min_keys keys; dead slots are not carried. Returns
+        the plan acted on (halvings == 0: the table was left alone)."""
+        r = ShrinkReport()
+        st = self._L.rl_shrink_limiter(self._h, int(limiter), int(now_ns), int(min_keys), ctypes.byref(r))
+        if st != RL_OK:
+            raise RlError(st, "rl_shrink_limiter")
+        return self._shrink_dict(r)
 
     def stats(self) -> dict:
         s = BatchStats()

@@ -467,10 +467,66 @@ int  rl_restore_keys(rl_engine* e, size_t n, const rl_key_image* in, size_t* n_p
 
 /* Background TTL sweep (Redis active expiry of the PEXPIRE deadlines set at
  * RedisRateLimitStorage.java:41-44 and Lua :64): frees every slot none of whose buckets is live at
- * now_ns, so table memory tracks live keys even for regions no batch touches. (Batches already
- * drop dead slots of the regions they load.) now_ns must not exceed the now of any later request,
- * as with Redis's own clock. *reclaimed (nullable) = slots freed. */
+ * now_ns, so used slots track live keys even for regions no batch touches. (Batches already
+ * drop dead slots of the regions they load.) The sweep frees slots, not memory: the allocation
+ * keeps its size; rl_shrink_limiter below gives table memory back. now_ns must not exceed the
+ * now of any later request, as with Redis's own clock. *reclaimed (nullable) = slots freed. */
 int  rl_sweep_expired(rl_engine* e, int64_t now_ns, uint64_t* reclaimed);
+
+/* ---- table shrink: give table memory back after a key flood --------------------------
+ * rl_grow_limiter and the automatic growth only ever double a limiter's region count; after a
+ * flood of one-off keys has expired, the table (32 B per slot, + 8 B with a local cache) and every
+ * slot-proportional pass (sweep, census, export, snapshot) would keep paying for the peak. The
+ * reference's Redis returns memory as keys expire; these two calls do it in place, with no second
+ * engine and no change to the limiter list.
+ * Regions 2r and 2r+1 of a table with k region bits are region r with k-1 bits (the split of
+ * rl_grow_limiter, read backwards), so a table halved i times has region r' = the regions
+ * r' << i ... (r' << i) + 2^i - 1 merged. With kept(r) = the slots of region r live at now =
+ * floorDiv(now_ns, 1e6) (the rule of rl_sweep_expired), fullest[i] is the largest sum of kept
+ * over one region of the table halved i times. halvings = j = the largest i < levels with
+ *   fullest[i] <= RL_SHRINK_FILL_MAX  and
+ *   slots_before >> i >= max(2 * ceil(min_keys / shard_count), 8 * 256)
+ * (the load <= 0.5 rule of rl_grow_limiter and the minimum of 8 regions); i = 0, no change, is
+ * always allowed. RL_SHRINK_FILL_MAX is half the fill at which a batch flags a limiter for growth
+ * (208 of 256 slots): the fullest region of a shrunk table must double its keys before the table
+ * grows again.
+ * rl_shrink_plan only reads: no state, cache word, batch statistic, and not the status
+ * rl_last_status reports (the standing of rl_limiter_usage). rl_shrink_limiter runs the same plan
+ * and, if j > 0, installs a table of 2^(k-j) regions holding exactly the kept slots, slot words
+ * and local-cache word bit for bit; slots dead at now and tombstones are not carried (a shrink
+ * includes that limiter's sweep, and now_ns has the restriction stated there). With j == 0 the
+ * table is not touched at all, not even swept, and the call returns RL_OK. *out (nullable for
+ * rl_shrink_limiter) receives the plan the call acted on. It works with RL_OPT_FIXED_CAPACITY
+ * too: it is an explicit call. Nothing shrinks on its own.
+ * Common rules, as for the census and snapshot calls: both run behind every batch submitted before
+ * them (RL_OPT_PIPELINE included) and synchronise; they work on the table as installed and neither
+ * change nor collect the batch status. A growth flag of an earlier batch that nobody has collected
+ * yet may grow the shrunk table once at the next collection: harmless, the table then has twice
+ * the room it needs. RL_E_INVALID_ARG, before any device call and with outputs untouched: a null
+ * engine (checked first), an unknown limiter, a null out in rl_shrink_plan.
+ * All or nothing: the new table is built in fresh allocations (j halvings in ceil(j / 3) passes
+ * through intermediate tables, each at most 1/8 of the one before; peak extra device memory =
+ * the new table, 1/2^j of the old one, for j <= 3, and less than 1/7 of the old one with the
+ * intermediates for j > 3, + 12 B per region of plan scratch);
+ * the old table is freed and the limiter record updated only after the last pass has succeeded.
+ * On RL_E_NOMEM, RL_E_DEVICE or RL_E_INTERNAL the old table is still installed and intact.
+ * Region ids of this and the later limiters change with a shrink as with a growth. */
+#define RL_SHRINK_FILL_MAX 104   /* = 208 / 2 */
+#define RL_SHRINK_LEVELS   24
+typedef struct rl_shrink_report {
+    uint64_t slots_before;   /* == rl_limiter_slots when the call ran                         */
+    uint64_t slots_after;    /* slots_before >> halvings                                      */
+    uint64_t used_before;    /* slots that were not free (live + dead + tombstones)           */
+    uint64_t kept;           /* slots live at now (the rule of rl_sweep_expired): carried over */
+    uint32_t halvings;       /* j: the region count is / would be divided by 2^j; 0 = no change */
+    uint32_t levels;         /* valid entries of fullest = region_bits - 3 + 1                 */
+    uint32_t fullest[RL_SHRINK_LEVELS]; /* fullest[i] = most kept slots in one region if the
+                                           region count were halved i times (non-decreasing)   */
+} rl_shrink_report;
+int  rl_shrink_plan(rl_engine* e, uint16_t limiter, int64_t now_ns, uint64_t min_keys,
+                    rl_shrink_report* out);
+int  rl_shrink_limiter(rl_engine* e, uint16_t limiter, int64_t now_ns, uint64_t min_keys,
+                       rl_shrink_report* out);
 
 /* ---- census of a limiter's table --------------------------------------------------
  * What DBSIZE / INFO keyspace / SCAN answer for the reference's Redis, computed on the device in
