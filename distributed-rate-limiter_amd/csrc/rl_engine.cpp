@@ -1744,14 +1744,15 @@ namespace rl {
 int route_pack_wire_mm(rl_engine* e, size_t n, const uint32_t* perm, const uint64_t* key,
                        const int32_t* permits, const int64_t* now_ns, const uint16_t* limiter,
                        uint64_t* wire_out, uint16_t* limiter_out, int64_t* hdr, uint64_t* part,
-                       uint32_t* nparts, void* stream) {
+                       uint32_t* nparts, void* stream, const int64_t* live_counts,
+                       uint32_t live_stride, uint32_t live_g) {
     if (!e || !hdr || !part || !nparts || (n && (!perm || !key || !permits || !now_ns || !wire_out)))
         return RL_E_INVALID_ARG;
     if (n > 0xFFFFFFF0ULL) return RL_E_TOO_LARGE;
     (void)hipSetDevice(e->device);
     hipStream_t s = stream ? (hipStream_t)stream : e->stream;
     HIP_OK(launch_route_pack_wire((uint32_t)n, perm, key, permits, now_ns, limiter, wire_out,
-                                  limiter_out, hdr, s, part, nparts));
+                                  limiter_out, hdr, s, part, nparts, live_counts, live_stride, live_g));
     return RL_OK;
 }
 int engine_device(rl_engine* e) { return e ? e->device : 0; }
@@ -1868,7 +1869,47 @@ extern "C" int rl_route_unpack_return(rl_engine* e, size_t n, const uint32_t* pe
 extern "C" int rl_route_partition_device(rl_engine* e, size_t n, const uint64_t* key_hash,
                                          uint32_t shard_count, uint32_t* perm, int64_t* counts_dev,
                                          size_t counts_stride, void* stream) {
-    if (!e || !key_hash || !perm || !counts_dev || counts_stride == 0) return RL_E_INVALID_ARG;
+    if (!e || !key_hash) return RL_E_INVALID_ARG;
+    return rl_route_partition_skip_device(e, n, key_hash, nullptr, shard_count, perm, counts_dev,
+                                          counts_stride, stream);
+}
+
+extern "C" int rl_route_fold_ops(rl_engine* e, size_t n, const uint32_t* perm, const uint16_t* limiter,
+                                 const uint8_t* op, uint16_t* col, void* stream) {
+    if (!e || (n && (!perm || !col))) return RL_E_INVALID_ARG;
+    if (n > 0xFFFFFFF0ULL) return RL_E_TOO_LARGE;
+    (void)hipSetDevice(e->device);
+    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    HIP_OK(launch_route_fold_ops((uint32_t)n, perm, limiter, op, col, s));
+    return RL_OK;
+}
+
+extern "C" int rl_route_unfold_ops(rl_engine* e, size_t m, const uint16_t* col, uint16_t* limiter_out,
+                                   uint8_t* op_out, void* stream) {
+    if (!e || (m && (!col || !limiter_out || !op_out))) return RL_E_INVALID_ARG;
+    if (m > 0xFFFFFFF0ULL) return RL_E_TOO_LARGE;
+    (void)hipSetDevice(e->device);
+    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    HIP_OK(launch_route_unfold_ops((uint32_t)m, col, limiter_out, op_out, s));
+    return RL_OK;
+}
+
+extern "C" int rl_route_unpack_wait(rl_engine* e, size_t n, size_t n_live, const uint32_t* perm,
+                                    const int64_t* back, const uint8_t* skip, int64_t* wait_ms,
+                                    void* stream) {
+    if (!e || n_live > n || (n && !wait_ms) || (n_live && (!perm || !back))) return RL_E_INVALID_ARG;
+    if (n > 0xFFFFFFF0ULL) return RL_E_TOO_LARGE;
+    (void)hipSetDevice(e->device);
+    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    HIP_OK(launch_route_unpack_wait((uint32_t)n, (uint32_t)n_live, perm, back, skip, wait_ms, s));
+    return RL_OK;
+}
+
+extern "C" int rl_route_partition_skip_device(rl_engine* e, size_t n, const uint64_t* key_hash,
+                                              const uint8_t* skip, uint32_t shard_count,
+                                              uint32_t* perm, int64_t* counts_dev,
+                                              size_t counts_stride, void* stream) {
+    if (!e || (n && !key_hash) || !perm || !counts_dev || counts_stride == 0) return RL_E_INVALID_ARG;
     if (shard_count == 0 || shard_count > 64 || (shard_count & (shard_count - 1))) return RL_E_INVALID_ARG;
     if (n > 0xFFFFFFF0ULL) return RL_E_TOO_LARGE;
     std::lock_guard<std::mutex> lk(e->mu);
@@ -1886,7 +1927,7 @@ extern "C" int rl_route_partition_device(rl_engine* e, size_t n, const uint64_t*
         HIP_OK(hipMemsetAsync(e->route_counts, 0, 64 * sizeof(uint32_t), s));
     } else {
         HIP_OK(launch_owner_partition(key_hash, (uint32_t)n, shard_count, perm, e->route_counts,
-                                      e->route_scratch, e->d_dir, s));
+                                      e->route_scratch, e->d_dir, s, skip));
     }
     HIP_OK(launch_counts_to_header(e->route_counts, shard_count, counts_dev, (uint32_t)counts_stride, s));
     return RL_OK;

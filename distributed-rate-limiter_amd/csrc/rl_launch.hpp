@@ -591,9 +591,11 @@ hipError_t launch_usage_digits(const UsageScratch& sc, const Slot* table, uint64
                                const DevLimiter& L, int64_t now_ms, const UsageSel& sel, hipStream_t s);
 hipError_t launch_usage_compact(const UsageScratch& sc, const Slot* table, uint64_t n_slots,
                                 const DevLimiter& L, int64_t now_ms, const UsageSel& sel, hipStream_t s);
+// skip (nullable): requests with skip[i] != 0 are neither counted nor placed; perm then holds
+// the others' stable owner order in its first sum(counts) entries
 hipError_t launch_owner_partition(const uint64_t* key, uint32_t n, uint32_t shard_count,
                                   uint32_t* perm, uint32_t* counts_dev, uint32_t* scratch,
-                                  const DirSlot* dir, hipStream_t s);
+                                  const DirSlot* dir, hipStream_t s, const uint8_t* skip = nullptr);
 
 hipError_t launch_route_pack(uint32_t n, const uint32_t* perm, const uint64_t* key,
                              const int32_t* permits, const int64_t* now, const uint16_t* lim,
@@ -609,7 +611,27 @@ constexpr uint32_t kWireBlocksMax = 2048;
 hipError_t launch_route_pack_wire(uint32_t n, const uint32_t* perm, const uint64_t* key,
                                   const int32_t* permits, const int64_t* now, const uint16_t* lim,
                                   uint64_t* wire, uint16_t* lim_o, int64_t* hdr, hipStream_t s,
-                                  uint64_t* part = nullptr, uint32_t* nparts = nullptr);
+                                  uint64_t* part = nullptr, uint32_t* nparts = nullptr,
+                                  const int64_t* live_counts = nullptr, uint32_t live_stride = 0,
+                                  uint32_t live_g = 0);
+// live_counts (nullable, device): only perm's first sum over q < live_g of
+// live_counts[q * live_stride] entries are requests (the counts a skip partition left on the
+// device); n then only bounds the grid, and the kernel takes the count where the partition
+// left it, so no host read separates the two.
+//
+// Mixed operations: the wire's u16 limiter column carries min(limiter, kOpsLimMask) |
+// min(op, 3) << kOpsShift (rl_route_fold_ops / rl_route_unfold_ops).
+constexpr uint32_t kOpsLimMask = 0x3FFF;
+constexpr uint32_t kOpsShift = 14;
+hipError_t launch_route_fold_ops(uint32_t n, const uint32_t* perm, const uint16_t* lim,
+                                 const uint8_t* op, uint16_t* col, hipStream_t s);
+hipError_t launch_route_unfold_ops(uint32_t m, const uint16_t* col, uint16_t* lim_o, uint8_t* op_o,
+                                   hipStream_t s);
+// wait[i] = 0 where skip[i] != 0 (skip nullable); wait[perm[j]] = back[j] for j < n_live
+hipError_t launch_route_unpack_wait(uint32_t n, uint32_t n_live, const uint32_t* perm,
+                                    const int64_t* back, const uint8_t* skip, int64_t* wait,
+                                    hipStream_t s);
+hipError_t launch_fill_i64(int64_t* out, uint32_t n, int64_t v, hipStream_t s);
 hipError_t launch_route_unwire(uint32_t m, const uint64_t* wire, uint32_t n_src, const int64_t* base,
                                const uint32_t* end, uint64_t* key_o, int32_t* permits_o,
                                int64_t* now_o, hipStream_t s);
@@ -660,7 +682,8 @@ hipError_t launch_status_accum(const BatchCtl* ctl, unsigned long long flags, un
 int route_pack_wire_mm(rl_engine* e, size_t n, const uint32_t* perm, const uint64_t* key,
                        const int32_t* permits, const int64_t* now_ns, const uint16_t* limiter,
                        uint64_t* wire_out, uint16_t* limiter_out, int64_t* hdr, uint64_t* part,
-                       uint32_t* nparts, void* stream);
+                       uint32_t* nparts, void* stream, const int64_t* live_counts = nullptr,
+                       uint32_t live_stride = 0, uint32_t live_g = 0);
 int engine_device(rl_engine* e);
 size_t engine_max_batch(rl_engine* e);
 size_t engine_limiters(rl_engine* e);

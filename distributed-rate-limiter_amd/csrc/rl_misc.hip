@@ -71,9 +71,23 @@ __device__ inline uint32_t owner_of_tag(uint64_t t, int sbits, const DirSlot* di
     return sbits ? (uint32_t)(t >> (64 - sbits)) : 0u;
 }
 
+// A request takes part in the partition when it is inside the batch and not skipped (skip:
+// nullable; rl_route_partition_skip_device hands a step's `allowed` back as the skip mask, so
+// that only the denials are counted and placed). The key is read for every request inside the
+// batch, skipped or not, so that both loads are in flight together and the skip byte's latency
+// does not come in front of the key's.
+__device__ inline bool owner_active(uint32_t i, uint32_t n, const uint64_t* key, const uint8_t* skip,
+                                    uint64_t& k) {
+    const bool in = i < n;
+    k = in ? key[i] : 0;
+    const uint8_t sk = in && skip ? skip[i] : (uint8_t)0;
+    return in && sk == 0;
+}
+
 __global__ __launch_bounds__(kTileThreads) void k_owner_count(const uint64_t* key, uint32_t n,
                                                               int sbits, uint32_t n_tiles,
-                                                              uint32_t* counts, const DirSlot* dir) {
+                                                              uint32_t* counts, const DirSlot* dir,
+                                                              const uint8_t* skip) {
     __shared__ uint32_t hist[64];
     const uint32_t t = threadIdx.x;
     if (t < 64) hist[t] = 0;
@@ -81,7 +95,8 @@ __global__ __launch_bounds__(kTileThreads) void k_owner_count(const uint64_t* ke
     const uint32_t tile = blockIdx.x;
     for (int r = 0; r < kTileItems; ++r) {
         const uint32_t i = tile * (uint32_t)kTile + (uint32_t)r * kTileThreads + t;
-        if (i < n) atomicAdd(&hist[owner_of_tag(mix64(key[i]), sbits, dir)], 1u);
+        uint64_t k;
+        if (owner_active(i, n, key, skip, k)) atomicAdd(&hist[owner_of_tag(mix64(k), sbits, dir)], 1u);
     }
     __syncthreads();
     if (t < (1u << sbits)) counts[(size_t)t * n_tiles + tile] = hist[t];
@@ -91,7 +106,8 @@ __global__ __launch_bounds__(kTileThreads) void k_owner_scatter(const uint64_t* 
                                                                 int sbits, uint32_t n_tiles,
                                                                 const uint32_t* counts,
                                                                 const uint32_t* bin_base,
-                                                                uint32_t* perm, const DirSlot* dir) {
+                                                                uint32_t* perm, const DirSlot* dir,
+                                                                const uint8_t* skip) {
     __shared__ uint32_t cur[64];
     __shared__ uint8_t cntw[kTileThreads / 64][64];
     const uint32_t t = threadIdx.x, wid = t >> 6;
@@ -104,8 +120,9 @@ __global__ __launch_bounds__(kTileThreads) void k_owner_scatter(const uint64_t* 
     __syncthreads();
     for (int r = 0; r < kTileItems; ++r) {
         const uint32_t i = tile * (uint32_t)kTile + (uint32_t)r * kTileThreads + t;
-        const bool active = i < n;
-        const uint32_t d = active ? owner_of_tag(mix64(key[i]), sbits, dir) : 0u;
+        uint64_t k;
+        const bool active = owner_active(i, n, key, skip, k);
+        const uint32_t d = active ? owner_of_tag(mix64(k), sbits, dir) : 0u;
         const uint64_t m = wave_match(d, sbits, active);
         const uint32_t lr = popc_below(m);
         const uint32_t c = (uint32_t)__popcll(m);
@@ -169,6 +186,11 @@ __global__ __launch_bounds__(256) void k_route_unpack(uint32_t n, const uint32_t
 // this source's batch, so any batch spanning < 2^31 ms each side of its first request is
 // exact; hdr[1] flags a request outside that range (the router then sends this step in
 // the wide layout). The engine floors now_ns to ms, so nothing it reads is lost.
+struct LiveCount {               // the live count of a skip partition, in device memory
+    const int64_t* counts;       // nullable: counts[q * stride], q < g, as the partition left them
+    uint32_t stride, g;
+};
+
 __global__ __launch_bounds__(256) void k_route_pack_wire(uint32_t n, const uint32_t* __restrict__ perm,
                                                          const uint64_t* __restrict__ key,
                                                          const int32_t* __restrict__ permits,
@@ -177,10 +199,24 @@ __global__ __launch_bounds__(256) void k_route_pack_wire(uint32_t n, const uint3
                                                          uint64_t* __restrict__ wire,
                                                          uint16_t* __restrict__ lim_o,
                                                          int64_t* __restrict__ hdr,
-                                                         uint64_t* __restrict__ part) {
+                                                         uint64_t* __restrict__ part,
+                                                         LiveCount live) {
     // grid-stride (a capped grid): with `part`, block b leaves the ordered-key min / max of
     // its requests' now_ms in part[2b], part[2b+1] (the router's header reduces them; no
     // atomics on one word, which sustains only ~88 adds per us)
+    // live.counts: only perm's first sum(counts) entries are requests (a skip partition left
+    // its per-owner counts there; the host does not know them yet). n bounds the grid; the
+    // base is request 0's time whether that request is among them or not.
+    if (live.counts) {
+        __shared__ uint32_t s_live;
+        if (threadIdx.x == 0) {
+            uint64_t t = 0;
+            for (uint32_t q = 0; q < live.g; ++q) t += (uint64_t)live.counts[(size_t)q * live.stride];
+            s_live = t < n ? (uint32_t)t : n;
+        }
+        __syncthreads();
+        n = s_live;
+    }
     const int64_t base = floor_div_ms(now[0]) - (1LL << 31);
     if (blockIdx.x == 0 && threadIdx.x == 0) hdr[0] = base;
     bool bad = false;
@@ -486,18 +522,19 @@ hipError_t launch_synth(const SynthArgs& a, hipStream_t s) {
 
 hipError_t launch_owner_partition(const uint64_t* key, uint32_t n, uint32_t shard_count,
                                   uint32_t* perm, uint32_t* counts_dev, uint32_t* scratch,
-                                  const DirSlot* dir, hipStream_t s) {
+                                  const DirSlot* dir, hipStream_t s, const uint8_t* skip) {
     int sbits = 0;
     while ((1u << sbits) < shard_count) ++sbits;
     const uint32_t nt = tiles_for(n);
     uint32_t* counts = scratch;                       // [shards][tiles]
     uint32_t* base = scratch + (size_t)shard_count * nt;
-    hipLaunchKernelGGL(k_owner_count, dim3(nt), dim3(kTileThreads), 0, s, key, n, sbits, nt, counts, dir);
+    hipLaunchKernelGGL(k_owner_count, dim3(nt), dim3(kTileThreads), 0, s, key, n, sbits, nt, counts, dir,
+                       skip);
     hipError_t e = launch_scan_rows(counts, counts, shard_count, nt, counts_dev, s);
     if (e == hipSuccess) e = launch_scan_small(counts_dev, base, shard_count, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_owner_scatter, dim3(nt), dim3(kTileThreads), 0, s, key, n, sbits, nt,
-                       counts, base, perm, dir);
+                       counts, base, perm, dir, skip);
     return hipGetLastError();
 }
 
@@ -530,14 +567,16 @@ hipError_t launch_route_unpack(uint32_t n, const uint32_t* perm, const int64_t* 
 hipError_t launch_route_pack_wire(uint32_t n, const uint32_t* perm, const uint64_t* key,
                                   const int32_t* permits, const int64_t* now, const uint16_t* lim,
                                   uint64_t* wire, uint16_t* lim_o, int64_t* hdr, hipStream_t s,
-                                  uint64_t* part, uint32_t* nparts) {
+                                  uint64_t* part, uint32_t* nparts, const int64_t* live_counts,
+                                  uint32_t live_stride, uint32_t live_g) {
     if (nparts) *nparts = 0;
     hipError_t e = hipMemsetAsync(hdr, 0, 2 * sizeof(int64_t), s);
     if (e != hipSuccess || n == 0) return e;
     const uint32_t blocks = std::min<uint32_t>((n + 255) / 256, kWireBlocksMax);
     if (nparts) *nparts = blocks;
     hipLaunchKernelGGL(k_route_pack_wire, dim3(blocks), dim3(256), 0, s, n, perm, key,
-                       permits, now, lim, wire, lim_o, hdr, part);
+                       permits, now, lim, wire, lim_o, hdr, part,
+                       LiveCount{live_counts, live_stride, live_g});
     return hipGetLastError();
 }
 
@@ -582,5 +621,80 @@ hipError_t launch_route_unpack_w(uint32_t n, const uint32_t* perm, const void* p
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ ops and retry-after queries
+// Mixed operations through the router: op rides in the u16 limiter column of the wire,
+// col = min(limiter, 0x3FFF) | min(op, 3) << 14. RL_MAX_LIMITERS is 255, so an id clamped to
+// 0x3FFF stays unknown and an op clamped to 3 stays invalid: neither can alias a valid pair.
+__global__ __launch_bounds__(256) void k_route_fold_ops(uint32_t n, const uint32_t* __restrict__ perm,
+                                                        const uint16_t* __restrict__ lim,
+                                                        const uint8_t* __restrict__ op,
+                                                        uint16_t* __restrict__ col) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t i = perm[j];
+    const uint32_t l = lim ? lim[i] : 0u, o = op ? op[i] : 0u;
+    col[j] = (uint16_t)((l < kOpsLimMask ? l : kOpsLimMask) | (o < 3u ? o : 3u) << kOpsShift);
+}
+
+// (no __restrict__: lim_o may be col itself; every thread reads its word before writing it)
+__global__ __launch_bounds__(256) void k_route_unfold_ops(uint32_t m, const uint16_t* col,
+                                                          uint16_t* lim_o, uint8_t* op_o) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const uint32_t c = col[j];
+    lim_o[j] = (uint16_t)(c & kOpsLimMask);
+    op_o[j] = (uint8_t)(c >> kOpsShift);
+}
+
+// The waits of a query exchange back in the caller's order, one launch: thread j zeroes its own
+// skipped query and scatters live answer j. The two sets of targets are disjoint (perm's first
+// n_live entries are exactly the queries with skip == 0).
+__global__ __launch_bounds__(256) void k_route_unpack_wait(uint32_t n, uint32_t n_live,
+                                                           const uint32_t* __restrict__ perm,
+                                                           const int64_t* __restrict__ back,
+                                                           const uint8_t* __restrict__ skip,
+                                                           int64_t* __restrict__ wait) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    if (skip && skip[j]) wait[j] = 0;
+    if (j < n_live) {
+        const uint32_t i = perm[j];
+        if (i < n) wait[i] = back[j];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_fill_i64(int64_t* out, uint32_t n, int64_t v) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = v;
+}
+
+hipError_t launch_route_fold_ops(uint32_t n, const uint32_t* perm, const uint16_t* lim,
+                                 const uint8_t* op, uint16_t* col, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_route_fold_ops, dim3((n + 255) / 256), dim3(256), 0, s, n, perm, lim, op, col);
+    return hipGetLastError();
+}
+
+hipError_t launch_route_unfold_ops(uint32_t m, const uint16_t* col, uint16_t* lim_o, uint8_t* op_o,
+                                   hipStream_t s) {
+    if (m == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_route_unfold_ops, dim3((m + 255) / 256), dim3(256), 0, s, m, col, lim_o, op_o);
+    return hipGetLastError();
+}
+
+hipError_t launch_route_unpack_wait(uint32_t n, uint32_t n_live, const uint32_t* perm,
+                                    const int64_t* back, const uint8_t* skip, int64_t* wait,
+                                    hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_route_unpack_wait, dim3((n + 255) / 256), dim3(256), 0, s, n, n_live, perm,
+                       back, skip, wait);
+    return hipGetLastError();
+}
+
+hipError_t launch_fill_i64(int64_t* out, uint32_t n, int64_t v, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_fill_i64, dim3((n + 255) / 256), dim3(256), 0, s, out, n, v);
+    return hipGetLastError();
+}
 
 }  // namespace rl

@@ -21,6 +21,9 @@
 // whole step in the wide SoA layout instead (every rank sees its overflow flag).
 // Errors are collective: each rank publishes its engine's status in the next header, so all
 // ranks fail at the same step.
+// rl_router_execute is that step with an operation per request (rl_router_step: none);
+// rl_router_retry_after runs the same exchange for the denials' waits (end of this file). The
+// round plan of all three is rl_exchange.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,6 +33,7 @@
 #include <vector>
 
 #include "../../include/rl_engine.h"
+#include "rl_exchange.hpp"
 #include "rl_launch.hpp"
 #include "rl_replan.hpp"
 
@@ -77,6 +81,7 @@ struct rl_router {
     // receive side (rcap)
     uint64_t* wire_r = nullptr;
     uint16_t* lim_r = nullptr;
+    uint8_t* op_r = nullptr;             // the operations decoded from lim_r (rl_router_execute)
     uint64_t* k_r = nullptr;
     int32_t* p_r = nullptr;
     int64_t* t_r = nullptr;
@@ -114,7 +119,7 @@ extern "C" void rl_router_destroy(rl_router* r) {
     if (r->done && r->stepped) (void)hipEventSynchronize(r->done);
     if (r->own) (void)hipStreamSynchronize(r->own);
     void* bufs[] = {r->perm, r->wire_s, r->lim_s, r->hdr2, r->mm_part, r->hdr, r->k_s, r->p_s, r->t_s,
-                    r->back_w, r->ret_in, r->dir, r->wire_r, r->lim_r, r->k_r, r->p_r, r->t_r, r->a_r,
+                    r->back_w, r->ret_in, r->dir, r->wire_r, r->lim_r, r->op_r, r->k_r, r->p_r, r->t_r, r->a_r,
                     r->rem_r, r->packed_r, r->ret_out, r->lost, r->acc};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
@@ -156,7 +161,7 @@ extern "C" int rl_router_create_ex(rl_engine* e, uint32_t world, uint32_t rank, 
     ok = ok && take(&r->hdr, 2 * (size_t)world * kHdrWords * 8) && take(&r->lost, 4);
     ok = ok && take(&r->dir, dir_words(world) * 8);
     ok = ok && take(&r->wire_r, m * 16) && take(&r->lim_r, m * 2) && take(&r->k_r, m * 8);
-    ok = ok && take(&r->p_r, m * 4) && take(&r->t_r, m * 8) && take(&r->a_r, m);
+    ok = ok && take(&r->p_r, m * 4) && take(&r->t_r, m * 8) && take(&r->a_r, m) && take(&r->op_r, m);
     ok = ok && take(&r->rem_r, m * 8) && take(&r->packed_r, m * 8) && take(&r->ret_out, r->ret_out_cap);
     ok = ok && take(&r->acc, kStatusAccWords * 8);
     ok = ok && hipMemset(r->lost, 0, 4) == hipSuccess;
@@ -235,10 +240,6 @@ static int64_t settle_pending(rl_router* r) {
     return st;
 }
 
-static uint64_t clampu(int64_t x, uint64_t hi) {
-    return x <= 0 ? 0 : ((uint64_t)x > hi ? hi : (uint64_t)x);
-}
-
 // Failure model (include/rl_engine.h: errors are collective). Before the header exchange a
 // step may fail on its own (bad arguments, a launch error: nothing has been sent). After
 // it, every rank goes through every collective of the step whatever happens locally: all
@@ -246,9 +247,14 @@ static uint64_t clampu(int64_t x, uint64_t hi) {
 // (RL_REMAINING_ERROR) and its status is published in the next header, and every rank
 // returns it at the same later step (or from rl_router_finish). Every rank derives the
 // step's exchange plan (rounds, per-pair ranges) from the same header rows.
-extern "C" int rl_router_step(rl_router* r, size_t n, const uint64_t* key, const int32_t* permits,
-                              const int64_t* now_ns, const uint16_t* limiter, uint8_t* allowed,
-                              int64_t* remaining, void* stream) {
+//
+// Operations (op != NULL) ride in the u16 limiter column (rl_route_fold_ops): the send side has
+// no room for a column of their own (the reservation bound of tests/cpp/test_router.cpp), the
+// owner decodes the column in place into lim_r and op_r. The column then travels whether or
+// not there are limiter ids, so the collectives are those of a step with `limiter`.
+extern "C" int rl_router_execute(rl_router* r, size_t n, const uint64_t* key, const int32_t* permits,
+                                 const int64_t* now_ns, const uint16_t* limiter, const uint8_t* op,
+                                 uint8_t* allowed, int64_t* remaining, void* stream) {
     if (!r) return RL_E_INVALID_ARG;
     if (n > r->cap) return RL_E_TOO_LARGE;          // caller error, before any collective
     if (n && (!key || !permits || !now_ns || !allowed || !remaining)) return RL_E_INVALID_ARG;
@@ -261,8 +267,10 @@ extern "C" int rl_router_step(rl_router* r, size_t n, const uint64_t* key, const
     // batch's now_ms range (per-block partials, folded by the header fill)
     R_RC(rl_route_partition_device(e, n, key, G, r->perm, hdr_s, kHdrWords, s));
     uint32_t nparts = 0;
+    const bool col = limiter || op;                  // the u16 column travels
     R_RC(route_pack_wire_mm(e, n, r->perm, key, permits, now_ns, limiter, r->wire_s,
-                            limiter ? r->lim_s : nullptr, r->hdr2, r->mm_part, &nparts, s));
+                            limiter && !op ? r->lim_s : nullptr, r->hdr2, r->mm_part, &nparts, s));
+    if (op) R_RC(rl_route_fold_ops(e, n, r->perm, limiter, op, r->lim_s, s));
     R_OK(launch_fill_header(hdr_s, r->hdr2, r->pub, (int64_t)r->cap, (int64_t)r->rcap, G, r->mm_part,
                             nparts, s));
     // 2. header exchange and the step's one host synchronisation
@@ -288,8 +296,6 @@ extern "C" int rl_router_step(rl_router* r, size_t n, const uint64_t* key, const
         cap_mismatch |= rcv[4] != (int64_t)r->cap || rcv[7] != (int64_t)r->rcap;
         if (rcv[0]) { tmin = std::min(tmin, rcv[5]); tmax = std::max(tmax, rcv[6]); }
     }
-    std::vector<uint64_t> counts(G), rc(G);         // mine to each owner, each source's to me
-    for (uint32_t p = 0; p < G; ++p) { counts[p] = C[(size_t)me * G + p]; rc[p] = C[(size_t)p * G + me]; }
     // the previous batch is complete (ordered before the header exchange): its status is
     // published in the next header; the statuses received now (every rank's batch two steps
     // back) are the same on all ranks, so all fail together
@@ -308,13 +314,11 @@ extern "C" int rl_router_step(rl_router* r, size_t n, const uint64_t* key, const
     }
     // rounds: each owner's incoming stream (sources in rank order = global arrival order)
     // is cut into pieces of at most rcap requests; round k moves piece k of every owner
-    uint64_t rounds = 1, m = 0;
-    for (uint32_t o = 0; o < G; ++o) {
-        uint64_t mo = 0;
-        for (uint32_t p = 0; p < G; ++p) mo += C[(size_t)p * G + o];
-        rounds = std::max<uint64_t>(rounds, (mo + r->rcap - 1) / r->rcap);
-        if (o == me) m = mo;
-    }
+    // (rl_exchange.hpp)
+    const ExchangePlan plan = exchange_plan(C, G, me, r->rcap);
+    const std::vector<uint64_t>& counts = plan.counts;   // mine to each owner
+    const std::vector<uint64_t>& rc = plan.rc;           // each source's to me
+    const uint64_t rounds = plan.rounds, m = plan.m;
     r->st.max_recv = std::max<uint64_t>(r->st.max_recv, m);
     r->st.rounds += rounds;
     int64_t local = RL_OK;                           // this step's own failure, published later
@@ -322,14 +326,15 @@ extern "C" int rl_router_step(rl_router* r, size_t n, const uint64_t* key, const
     if (!wide && rounds == 1) {
         // 3. payload: 16-B wire records (+ limiter ids)
         R_RC(a2av(r, r->wire_s, counts, r->wire_r, rc, 16, s));
-        if (limiter) R_RC(a2av(r, r->lim_s, counts, r->lim_r, rc, 2, s));
+        if (col) R_RC(a2av(r, r->lim_s, counts, r->lim_r, rc, 2, s));
+        if (op) R_RC(rl_route_unfold_ops(e, m, r->lim_r, r->lim_r, r->op_r, s));
         R_RC(rl_route_unwire(e, m, r->wire_r, G, base.data(), rc.data(), r->k_r, r->p_r, r->t_r, s));
         // 4. the owner decides. The merged batch spans the sources' real time range; past
         // what the engine's compact records hold (+-2^31 ms around its first request) it runs
         // in full-width records (skewed clocks across front-ends).
         if (far) (void)rl_tune(e, "wide_records", 1);
-        const int xrc = rl_execute_batch_device(e, m, r->k_r, r->p_r, r->t_r, limiter ? r->lim_r : nullptr,
-                                                nullptr, r->a_r, r->rem_r, nullptr, s);
+        const int xrc = rl_execute_batch_device(e, m, r->k_r, r->p_r, r->t_r, col ? r->lim_r : nullptr,
+                                                op ? r->op_r : nullptr, r->a_r, r->rem_r, nullptr, s);
         if (far) (void)rl_tune(e, "wide_records", 0);
         if (xrc != RL_OK) {
             local = xrc;
@@ -354,46 +359,32 @@ extern "C" int rl_router_step(rl_router* r, size_t n, const uint64_t* key, const
         // Wide layout (a source's batch spans more than 2^31 ms: SoA payload) and/or several
         // rounds (some owner receives more than rcap requests): 8-B decisions back into
         // back_w at each request's owner-order position, one unpack at the end.
+        // (the column is already in lim_s: the wire pack or the ops fold wrote it)
         if (wide) R_RC(rl_route_pack(e, n, r->perm, key, permits, now_ns, limiter, r->k_s, r->p_s,
-                                     r->t_s, limiter ? r->lim_s : nullptr, s));
+                                     r->t_s, nullptr, s));
         if (rounds > 1) ++r->st.split_steps;
-        const std::vector<uint64_t> seg = offsets(counts);
-        std::vector<uint64_t> Pm(G, 0), Q(G, 0);      // my start in each owner's stream; sources' in mine
-        for (uint32_t o = 0; o < G; ++o)
-            for (uint32_t p = 0; p < me; ++p) Pm[o] += C[(size_t)p * G + o];
-        for (uint32_t p = 1; p < G; ++p) Q[p] = Q[p - 1] + rc[p - 1];
         for (uint64_t k = 0; k < rounds; ++k) {
-            const int64_t lo_w = (int64_t)(k * r->rcap), hi_w = (int64_t)((k + 1) * r->rcap);
-            std::vector<uint64_t> so(G), sc(G), rr(G);
-            for (uint32_t o = 0; o < G; ++o) {
-                const uint64_t lo = clampu(lo_w - (int64_t)Pm[o], counts[o]);
-                const uint64_t hi = clampu(hi_w - (int64_t)Pm[o], counts[o]);
-                so[o] = seg[o] + lo;
-                sc[o] = hi - lo;
-            }
-            uint64_t mk = 0;
-            for (uint32_t p = 0; p < G; ++p) {
-                rr[p] = clampu(hi_w - (int64_t)Q[p], rc[p]) - clampu(lo_w - (int64_t)Q[p], rc[p]);
-                mk += rr[p];
-            }
-            const std::vector<uint64_t> ro = offsets(rr);
+            const ExchangeRound X = exchange_round(plan, k);
+            const std::vector<uint64_t>&so = X.so, &sc = X.sc, &ro = X.ro, &rr = X.rr;
+            const uint64_t mk = X.mk;
             if (!wide) {
                 R_RC(a2av_at(r, r->wire_s, so.data(), sc.data(), r->wire_r, ro.data(), rr.data(), 16, s));
-                if (limiter)
+                if (col)
                     R_RC(a2av_at(r, r->lim_s, so.data(), sc.data(), r->lim_r, ro.data(), rr.data(), 2, s));
                 R_RC(rl_route_unwire(e, mk, r->wire_r, G, base.data(), rr.data(), r->k_r, r->p_r, r->t_r, s));
             } else {
                 R_RC(a2av_at(r, r->k_s, so.data(), sc.data(), r->k_r, ro.data(), rr.data(), 8, s));
                 R_RC(a2av_at(r, r->p_s, so.data(), sc.data(), r->p_r, ro.data(), rr.data(), 4, s));
                 R_RC(a2av_at(r, r->t_s, so.data(), sc.data(), r->t_r, ro.data(), rr.data(), 8, s));
-                if (limiter)
+                if (col)
                     R_RC(a2av_at(r, r->lim_s, so.data(), sc.data(), r->lim_r, ro.data(), rr.data(), 2, s));
             }
+            if (op) R_RC(rl_route_unfold_ops(e, mk, r->lim_r, r->lim_r, r->op_r, s));
             const bool w = wide || far;
             if (w) (void)rl_tune(e, "wide_records", 1);
             const int xrc = rl_execute_batch_device(e, mk, r->k_r, r->p_r, r->t_r,
-                                                    limiter ? r->lim_r : nullptr, nullptr, r->a_r,
-                                                    r->rem_r, nullptr, s);
+                                                    col ? r->lim_r : nullptr, op ? r->op_r : nullptr,
+                                                    r->a_r, r->rem_r, nullptr, s);
             if (w) (void)rl_tune(e, "wide_records", 0);
             if (xrc != RL_OK) {
                 local = worse(local, xrc);
@@ -414,6 +405,12 @@ extern "C" int rl_router_step(rl_router* r, size_t n, const uint64_t* key, const
     R_OK(hipEventRecord(r->done, s));
     r->stepped = true;
     return RL_OK;
+}
+
+extern "C" int rl_router_step(rl_router* r, size_t n, const uint64_t* key, const int32_t* permits,
+                              const int64_t* now_ns, const uint16_t* limiter, uint8_t* allowed,
+                              int64_t* remaining, void* stream) {
+    return rl_router_execute(r, n, key, permits, now_ns, limiter, nullptr, allowed, remaining, stream);
 }
 
 extern "C" int rl_router_finish(rl_router* r) {
@@ -690,4 +687,95 @@ extern "C" int rl_router_replan_directory_sampled(rl_router* r, size_t n, const 
     std::vector<uint64_t> key, cnt;
     const int mine = sample_candidates(r, n, key_hash, k, min_count, s, &key, &cnt);
     return replan(r, key.size(), key.data(), cnt.data(), (uint64_t)n, k, placed, moved, mine, s);
+}
+
+// ---------------------------------------------------------------- retry-after, collectively
+// The step's exchange with three differences: only the queries with skip == 0 are placed
+// (rl_route_partition_skip_device; the wire pack takes their count from the header column on
+// the device, where the partition left it, since the host learns it only from the header
+// read), the owner answers with rl_retry_after_device into rem_r, and the waits come back
+// 8 B each into back_w at the query's owner-order position, whatever the number of rounds.
+// It reads and writes none of pub / held / pending / acc and none of the step statistics; its
+// header row carries status 0 and the received statuses are not looked at.
+//
+// Failure model: argument errors and launch errors before the header exchange return at once
+// (nothing has been sent). After it every rank goes through every collective: a local failure
+// is kept in `local`, an owner that could not answer sends RL_RETRY_ERROR, and one status row
+// (gather_rows, as the re-plan's) makes every rank return the worst status.
+extern "C" int rl_router_retry_after(rl_router* r, size_t n, const uint64_t* key, const int32_t* permits,
+                                     const int64_t* now_ns, const uint16_t* limiter,
+                                     const uint8_t* skip, int64_t* wait_ms, void* stream) {
+    if (!r) return RL_E_INVALID_ARG;
+    if (n > r->cap) return RL_E_TOO_LARGE;          // caller error, before any collective
+    if (n && (!key || !permits || !now_ns || !wait_ms)) return RL_E_INVALID_ARG;
+    hipStream_t s = stream ? (hipStream_t)stream : r->own;
+    const uint32_t G = r->world, me = r->rank;
+    rl_engine* e = r->e;
+    int64_t* hdr_s = r->hdr;
+    int64_t* hdr_r = r->hdr + (size_t)G * kHdrWords;
+    // behind this rank's previous step: its queued work still uses the exchange buffers
+    if (r->stepped) R_OK(hipStreamWaitEvent(s, r->done, 0));
+    R_RC(rl_route_partition_skip_device(e, n, key, skip, G, r->perm, hdr_s, kHdrWords, s));
+    uint32_t nparts = 0;
+    R_RC(route_pack_wire_mm(e, n, r->perm, key, permits, now_ns, limiter, r->wire_s,
+                            limiter ? r->lim_s : nullptr, r->hdr2, r->mm_part, &nparts, s, hdr_s,
+                            kHdrWords, G));
+    R_OK(launch_fill_header(hdr_s, r->hdr2, RL_OK, (int64_t)r->cap, (int64_t)r->rcap, G, r->mm_part,
+                            nparts, s));
+    const std::vector<uint64_t> hw(G, kHdrWords);
+    R_RC(a2av(r, hdr_s, hw, hdr_r, hw, 8, s));
+    R_OK(hipMemcpyAsync(r->h_hdr, r->hdr, 2 * (size_t)G * kHdrWords * 8, hipMemcpyDeviceToHost, s));
+    R_OK(hipStreamSynchronize(s));
+    std::vector<uint64_t> C((size_t)G * G);
+    std::vector<int64_t> base(G);
+    bool wide = false, cap_mismatch = false;
+    for (uint32_t p = 0; p < G; ++p) {
+        const int64_t* rcv = r->h_hdr + (size_t)(G + p) * kHdrWords;
+        for (uint32_t o = 0; o < G; ++o) C[(size_t)p * G + o] = (uint64_t)rcv[kHdrFixed + o];
+        base[p] = rcv[1];
+        wide |= rcv[2] != 0;
+        cap_mismatch |= rcv[4] != (int64_t)r->cap || rcv[7] != (int64_t)r->rcap;
+    }
+    if (cap_mismatch) {                              // seen by every rank: all return here
+        R_OK(launch_fill_i64(wait_ms, (uint32_t)n, RL_RETRY_ERROR, s));
+        R_OK(hipStreamSynchronize(s));
+        return RL_E_INVALID_ARG;
+    }
+    const ExchangePlan plan = exchange_plan(C, G, me, r->rcap);
+    uint64_t n_live = 0;
+    for (uint32_t o = 0; o < G; ++o) n_live += plan.counts[o];
+    int64_t local = RL_OK;
+    auto keep = [&](int rc) { if (rc != RL_OK) local = worse(local, rc); return rc; };
+    auto hip = [&](hipError_t x) { return x == hipSuccess ? RL_OK : RL_E_DEVICE; };
+    if (wide) keep(rl_route_pack(e, n_live, r->perm, key, permits, now_ns, limiter, r->k_s, r->p_s,
+                                 r->t_s, nullptr, s));
+    for (uint64_t k = 0; k < plan.rounds; ++k) {
+        const ExchangeRound X = exchange_round(plan, k);
+        const uint64_t *so = X.so.data(), *sc = X.sc.data(), *ro = X.ro.data(), *rr = X.rr.data();
+        int orc = RL_OK;                             // can this owner answer the round?
+        if (!wide) {
+            orc = worse(orc, keep(a2av_at(r, r->wire_s, so, sc, r->wire_r, ro, rr, 16, s)));
+            if (limiter) orc = worse(orc, keep(a2av_at(r, r->lim_s, so, sc, r->lim_r, ro, rr, 2, s)));
+            if (orc == RL_OK)
+                orc = keep(rl_route_unwire(e, X.mk, r->wire_r, G, base.data(), rr, r->k_r, r->p_r, r->t_r, s));
+        } else {
+            orc = worse(orc, keep(a2av_at(r, r->k_s, so, sc, r->k_r, ro, rr, 8, s)));
+            orc = worse(orc, keep(a2av_at(r, r->p_s, so, sc, r->p_r, ro, rr, 4, s)));
+            orc = worse(orc, keep(a2av_at(r, r->t_s, so, sc, r->t_r, ro, rr, 8, s)));
+            if (limiter) orc = worse(orc, keep(a2av_at(r, r->lim_s, so, sc, r->lim_r, ro, rr, 2, s)));
+        }
+        if (orc == RL_OK)
+            orc = keep(rl_retry_after_device(e, X.mk, r->k_r, r->p_r, r->t_r, limiter ? r->lim_r : nullptr,
+                                             nullptr, r->rem_r, s));
+        if (orc != RL_OK) keep(hip(launch_fill_i64(r->rem_r, (uint32_t)X.mk, RL_RETRY_ERROR, s)));
+        keep(a2av_at(r, r->rem_r, ro, rr, r->back_w, so, sc, 8, s));
+    }
+    keep(rl_route_unpack_wait(e, n, n_live, r->perm, r->back_w, skip, wait_ms, s));
+    // one status row, then the synchronous end (gather_rows synchronises the stream)
+    std::vector<uint64_t> row;
+    const uint64_t mine[1] = {(uint64_t)local};
+    R_RC(gather_rows(r, mine, 1, &row, s));
+    int64_t worst = RL_OK;
+    for (uint32_t p = 0; p < G; ++p) worst = worse(worst, (int64_t)row[p]);
+    return (int)worst;
 }

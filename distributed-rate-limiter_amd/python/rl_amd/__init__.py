@@ -31,6 +31,7 @@ SW, TB = 0, 1
 OP_ACQUIRE, OP_PEEK, OP_RESET = 0, 1, 2
 REM_UNKNOWN, REM_INVALID, REM_ERROR = -1, -2, -3
 RETRY_NEVER, RETRY_INVALID = -1, -2   # RL_RETRY_* (rl_retry_after)
+RETRY_ERROR = -3                      # RL_RETRY_ERROR (rl_router_retry_after: the owner's call failed)
 TOP_KEYS_MAX, TOP_KEYS_CANDIDATES = 4096, 65536   # RL_TOP_KEYS_* (rl_top_keys)
 USAGE_BINS, USAGE_CANDIDATES = 16, 65536   # RL_USAGE_* (rl_limiter_usage, rl_top_consumers)
 MOVE_KEYS_MAX = 8192                       # RL_MOVE_KEYS_MAX: keys per rl_copy_keys / rl_drop_keys
@@ -64,6 +65,8 @@ EXPORTS = [
     "rl_router_replan_directory", "rl_router_replan_directory_sampled",
     "rl_snapshot_keys", "rl_snapshot_keys_device", "rl_put_keys_device", "rl_restore_keys",
     "rl_shrink_plan", "rl_shrink_limiter",
+    "rl_router_execute", "rl_router_retry_after", "rl_route_partition_skip_device",
+    "rl_route_fold_ops", "rl_route_unfold_ops", "rl_route_unpack_wait",
 ]
 RCCL_EXPORTS = ["rl_rccl_unique_id", "rl_transport_rccl_create", "rl_transport_rccl_destroy"]
 STATE_SW_BUCKET, STATE_TB_BUCKET = 0, 1
@@ -240,6 +243,12 @@ def lib():
     L.rl_restore_keys.argtypes = [vp, sz, vp, ctypes.POINTER(sz)]
     L.rl_shrink_plan.argtypes = [vp, u16, i64, ctypes.c_uint64, ctypes.POINTER(ShrinkReport)]
     L.rl_shrink_limiter.argtypes = [vp, u16, i64, ctypes.c_uint64, ctypes.POINTER(ShrinkReport)]
+    L.rl_route_partition_skip_device.argtypes = [vp, sz, vp, vp, u32, vp, vp, sz, vp]
+    L.rl_route_fold_ops.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    L.rl_route_unfold_ops.argtypes = [vp, sz, vp, vp, vp, vp]
+    L.rl_route_unpack_wait.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp]
+    L.rl_router_execute.argtypes = [vp, sz] + [vp] * 8
+    L.rl_router_retry_after.argtypes = [vp, sz] + [vp] * 7
     _lib = L
     return L
 
@@ -801,6 +810,35 @@ class Engine:
                                                _p(counts_dev), stride, _p(stream))
         if st != RL_OK:
             raise RlError(st, "rl_route_partition_device")
+
+    def route_partition_skip_device(self, n, keys_dev, skip_dev, perm_dev, shard_count, counts_dev,
+                                    stride, stream=None):
+        """rl_route_partition_skip_device: the owner partition of the requests with skip == 0
+        (skip_dev None: all of them); the live counts land in counts_dev[s * stride]."""
+        st = self._L.rl_route_partition_skip_device(self._h, n, _p(keys_dev), _p(skip_dev),
+                                                    shard_count, _p(perm_dev), _p(counts_dev),
+                                                    stride, _p(stream))
+        if st != RL_OK:
+            raise RlError(st, "rl_route_partition_skip_device")
+
+    def route_fold_ops(self, n, perm, limiter, op, col, stream=None):
+        """col[j] = min(limiter[perm[j]], 0x3FFF) | min(op[perm[j]], 3) << 14 (either None: 0)."""
+        st = self._L.rl_route_fold_ops(self._h, n, _p(perm), _p(limiter), _p(op), _p(col), _p(stream))
+        if st != RL_OK:
+            raise RlError(st, "rl_route_fold_ops")
+
+    def route_unfold_ops(self, m, col, limiter_o, op_o, stream=None):
+        """limiter_o[j] = col[j] & 0x3FFF, op_o[j] = col[j] >> 14 (limiter_o may be col)."""
+        st = self._L.rl_route_unfold_ops(self._h, m, _p(col), _p(limiter_o), _p(op_o), _p(stream))
+        if st != RL_OK:
+            raise RlError(st, "rl_route_unfold_ops")
+
+    def route_unpack_wait(self, n, n_live, perm, back, skip, wait, stream=None):
+        """wait[i] = 0 where skip[i] != 0; wait[perm[j]] = back[j] for j < n_live."""
+        st = self._L.rl_route_unpack_wait(self._h, n, n_live, _p(perm), _p(back), _p(skip), _p(wait),
+                                          _p(stream))
+        if st != RL_OK:
+            raise RlError(st, "rl_route_unpack_wait")
 
     def synth_trace(self, n, keys, permits, now_ns, limiter, *, seed, n_keys, dist=DIST_UNIFORM,
                     zipf_s=1.1, permits_max=4, t0_ns=1_700_000_000_000 * 1_000_000,

@@ -113,7 +113,8 @@ class RouterStats(ctypes.Structure):
 
 
 class CRouter:
-    """rl_router_create_ex / step / finish / plan_directory / stats / destroy over one engine.
+    """rl_router_create_ex / step / execute / retry_after / finish / plan_directory / stats /
+    destroy over one engine.
     recv_cap: requests the owner's engine decides per exchange round (0: min(world, 2) x
     max_batch, clamped to the engine's max_batch); a step in which an owner receives more
     is split into rounds by every rank alike."""
@@ -170,6 +171,27 @@ class CRouter:
         if st < 0 and st != rl_amd.RL_E_INVALID_REQUEST:
             raise rl_amd.RlError(st, "rl_router_step")
         return st
+
+    def execute(self, n, keys, permits, now_ns, limiter, ops, allowed, remaining, stream=None):
+        """A step with operations (rl_router_execute; collective). ops (uint8 RL_OP_*) is None on
+        every rank or on none, as limiter; ops None is step()."""
+        p = rl_amd._p
+        st = self._L.rl_router_execute(self._h, n, p(keys), p(permits), p(now_ns), p(limiter),
+                                       p(ops), p(allowed), p(remaining), p(stream))
+        if st < 0 and st != rl_amd.RL_E_INVALID_REQUEST:
+            raise rl_amd.RlError(st, "rl_router_execute")
+        return st
+
+    def retry_after(self, n, keys, permits, now_ns, limiter, skip, wait, stream=None):
+        """The waits of this rank's queries from their keys' owners (rl_router_retry_after;
+        collective, between steps, synchronous): wait[i] in ms, RETRY_NEVER, RETRY_INVALID, 0
+        where skip[i] != 0. Raises on a fatal status (the same on every rank); the queries an
+        owner could not answer read RETRY_ERROR."""
+        p = rl_amd._p
+        st = self._L.rl_router_retry_after(self._h, n, p(keys), p(permits), p(now_ns), p(limiter),
+                                           p(skip), p(wait), p(stream))
+        if st != rl_amd.RL_OK:
+            raise rl_amd.RlError(st, "rl_router_retry_after")
 
     def finish(self) -> int:
         st = self._L.rl_router_finish(self._h)

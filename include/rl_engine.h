@@ -237,7 +237,8 @@ int  rl_reset(rl_engine* e, uint16_t limiter, size_t n, const uint64_t* key_hash
  * denials cost a lookup. The call changes nothing: no state, no cache entry, no batch
  * statistic, not the status rl_last_status reports. A sliding-window query whose now lies
  * before the key's newest INCR (time regression) is searched from that INCR's time; its wait
- * still counts from now. Multi-GPU: ask the key's owner, as with the batch calls.
+ * still counts from now. Multi-GPU: ask the key's owner, as with the batch calls
+ * (rl_router_retry_after does that for a whole batch of queries, collectively).
  * `limiter` and `skip` may be NULL (limiter 0, nothing skipped). */
 #define RL_RETRY_NEVER   (-1)
 #define RL_RETRY_INVALID (-2)
@@ -658,6 +659,30 @@ uint32_t rl_owner_of_engine(rl_engine* e, uint64_t key_hash);
 int  rl_route_partition_device(rl_engine* e, size_t n, const uint64_t* key_hash,
                                uint32_t shard_count, uint32_t* perm, int64_t* counts_dev,
                                size_t counts_stride, void* stream);
+/* rl_route_partition_device restricted to the requests with skip[i] == 0 (skip NULL: none is
+ * skipped, the call is rl_route_partition_device): perm[0 .. n_live) is the stable owner order
+ * of the live requests, counts_dev[s * counts_stride] the live count for shard s, n_live the sum
+ * of the counts; perm[n_live .. n) is not written. The directory is honoured. A caller hands a
+ * step's own key array and its `allowed` output as skip, and only the denials are placed. */
+int  rl_route_partition_skip_device(rl_engine* e, size_t n, const uint64_t* key_hash,
+                                    const uint8_t* skip, uint32_t shard_count, uint32_t* perm,
+                                    int64_t* counts_dev, size_t counts_stride, void* stream);
+/* Mixed operations on the wire: op rides in the u16 limiter column,
+ *   col[j] = min(limiter[perm[j]], 0x3FFF) | min(op[perm[j]], 3) << 14   (limiter / op nullable: 0)
+ * RL_MAX_LIMITERS is 255, so an id clamped to 0x3FFF stays unknown and an op clamped to 3 stays
+ * invalid: 0x4001 comes out as an unknown limiter, never as limiter 1 with RL_OP_PEEK. */
+int  rl_route_fold_ops(rl_engine* e, size_t n, const uint32_t* perm, const uint16_t* limiter,
+                       const uint8_t* op, uint16_t* col, void* stream);
+/* limiter_out[j] = col[j] & 0x3FFF, op_out[j] = col[j] >> 14; limiter_out may alias col */
+int  rl_route_unfold_ops(rl_engine* e, size_t m, const uint16_t* col, uint16_t* limiter_out,
+                         uint8_t* op_out, void* stream);
+/* The answers of a query exchange back in the caller's order, one launch: wait_ms[i] = 0 where
+ * skip[i] != 0 (skip nullable), wait_ms[perm[j]] = back[j] for j < n_live (perm from
+ * rl_route_partition_skip_device with the same skip; n_live <= n). */
+int  rl_route_unpack_wait(rl_engine* e, size_t n, size_t n_live, const uint32_t* perm,
+                          const int64_t* back, const uint8_t* skip, int64_t* wait_ms, void* stream);
+/* The four calls above take device buffers, run on `stream` (NULL: the engine's) and return
+ * argument or launch status. */
 
 /* ---- multi-GPU router ----------------------------------------
  * The reference's "distribution" is many app instances sharing one Redis
@@ -686,9 +711,9 @@ typedef struct rl_router_opts {
                                    step in which some owner receives more runs in several
                                    rounds (every rank derives the same plan from the header)   */
 } rl_router_opts;
-/* Every device buffer a step uses is reserved here (send side ~50 B x max_batch, receive
- * side ~56 B x recv_cap, the return trip, the directory exchange), so a step never
- * allocates between two collectives. rl_router_create = _ex with recv_cap 0. */
+/* Every device buffer a step, an execute or a query uses is reserved here (send side ~50 B x
+ * max_batch, receive side ~57 B x recv_cap, the return trip, the directory exchange), so none
+ * of them allocates between two collectives. rl_router_create = _ex with recv_cap 0. */
 int  rl_router_create_ex(rl_engine* e, uint32_t world, uint32_t rank, const rl_transport* t,
                          const rl_router_opts* opts, rl_router** out);
 int  rl_router_create(rl_engine* e, uint32_t world, uint32_t rank, const rl_transport* t,
@@ -720,6 +745,56 @@ int  rl_router_stats_get(rl_router* r, rl_router_stats* out);
 int  rl_router_step(rl_router* r, size_t n, const uint64_t* key_hash, const int32_t* permits,
                     const int64_t* now_ns, const uint16_t* limiter, uint8_t* allowed,
                     int64_t* remaining, void* stream);
+/* A step with operations (RL_OP_*; device buffers): allowed[i] / remaining[i] are what
+ * rl_execute_batch gives for request i on one unsharded engine fed the ranks' slices
+ * concatenated in rank order, step after step; peeks and resets are applied in array order with
+ * the acquires of the same key. op > 2 and unknown limiter ids are invalid exactly as on a
+ * single engine (RL_REMAINING_INVALID; rl_router_finish reports RL_E_INVALID_REQUEST).
+ * rl_router_step(...) is rl_router_execute(..., op = NULL, ...): the same collectives with the
+ * same byte counts, error model, statistics and results.
+ * `op` is NULL on every rank or on none, and so is `limiter` (a rank with n = 0 passes any
+ * non-NULL pointer): both decide which collectives a step makes.
+ * op travels in the u16 limiter column (rl_route_fold_ops; the owner decodes it in place with
+ * rl_route_unfold_ops), so with op != NULL the column travels even when limiter == NULL
+ * (limiter 0), and an execute with op makes exactly as many all_to_all_v calls as a step with
+ * limiter, in the compact, wide and split-round modes alike. */
+int  rl_router_execute(rl_router* r, size_t n, const uint64_t* key_hash, const int32_t* permits,
+                       const int64_t* now_ns, const uint16_t* limiter, const uint8_t* op,
+                       uint8_t* allowed, int64_t* remaining, void* stream);
+/* Retry-after for this rank's queries (device buffers), collectively: every rank calls it,
+ * between steps. wait_ms[i] is what rl_retry_after on one unsharded engine holding all keys'
+ * state would answer for query i (RL_RETRY_NEVER and RL_RETRY_INVALID included; 0 for
+ * skip[i] != 0); the key's owner answers, directory owners included, with
+ * rl_retry_after_device. `limiter` is NULL on every rank or on none; `skip` is local and may be
+ * NULL. n <= max_batch, else RL_E_TOO_LARGE before any collective; null arguments as for the
+ * step; n = 0 is valid and still takes part in the collectives.
+ * Only the queries with skip == 0 travel: 16 B forward in the compact wire (+ 2 B with
+ * `limiter`) and 8 B back, so a caller hands a step's arrays and its `allowed` output straight
+ * back and the exchange carries the denials only. The wide layout (a source whose travelling
+ * queries span more than 2^31 ms either side of now_ns[0], which is the base whether query 0 is
+ * skipped or not) and several rounds (an owner receives more than recv_cap queries) as the step.
+ * It uses the buffers rl_router_create_ex reserved and allocates nothing.
+ * Ordering: behind this rank's previous step, and on each owner behind every batch its engine
+ * was given before (rl_retry_after_device's rule, RL_OPT_PIPELINE included).
+ * It changes nothing: no limiter state, cache word or batch statistic, not the engine status,
+ * not the statuses the router holds for its next header, not rl_router_stats' steps / rounds /
+ * split_steps / max_recv; the header row it exchanges carries status 0.
+ * Synchronous end: after the return trip the ranks exchange one status row, the call
+ * synchronises the stream and returns the worst status of all ranks, the same on every rank:
+ * RL_OK or a fatal one. After the header exchange every rank goes through every collective of
+ * the call whatever fails locally; an owner whose rl_retry_after_device fails answers
+ * RL_RETRY_ERROR for the queries it received. A capacity mismatch between ranks (max_batch /
+ * recv_cap) is detected from the header as in the step: every rank returns RL_E_INVALID_ARG
+ * and its wait_ms[0..n) all read RL_RETRY_ERROR. Invalid queries do not make the call fail.
+ * A query's now may lie before requests the owner has decided since (a rank asks about its own
+ * slice after the whole step; the rounds of a split step are separate engine batches): state is
+ * kept for such timestamps for rl_opts.max_skew_ms, as for lagging requests, so the answers for
+ * a step's own timestamps are those of one unsharded engine when max_skew_ms covers the
+ * step's time span. */
+#define RL_RETRY_ERROR (-3)   /* query not answered: its owner's call failed (router form only) */
+int  rl_router_retry_after(rl_router* r, size_t n, const uint64_t* key_hash, const int32_t* permits,
+                           const int64_t* now_ns, const uint16_t* limiter, const uint8_t* skip,
+                           int64_t* wait_ms, void* stream);
 /* Collective: the worst status of every rank's last batches (all ranks get the same). */
 int  rl_router_finish(rl_router* r);
 /* Hot-key directory for the whole router (collective, before any state exists for the
