@@ -196,6 +196,10 @@ struct rl_engine {
     void* topk = nullptr;                   // rl_top_keys scratch (topk_scratch_bytes), on first use
     void* usage = nullptr;                  // rl_limiter_usage / rl_top_consumers scratch, on first use
     uint32_t usage_passes = 0;              // table passes of the last rl_top_consumers (rl_debug_fetch)
+    BucketDigest* digest = nullptr;         // [digest_cap] the host form of rl_limiter_digest, largest so far
+    size_t digest_cap = 0;
+    BucketDigest* digest_fine = nullptr;    // [2^kDigestFineBits] the pass' output when fewer buckets are asked for
+    uint32_t digest_per_cu = 0;             // rl_tune("digest_per_cu"), 0 = default
     void* snap = nullptr;                   // snapshot / ordered-put scratch (snap_scratch_bytes), on first use
     uint32_t* put_heads = nullptr;          // [put_heads_cap] run heads of an ordered put
     size_t put_heads_cap = 0;
@@ -402,7 +406,7 @@ extern "C" void rl_destroy(rl_engine* e) {
     dfree(e->walk_tab);
     dfree(e->route_list); dfree(e->route_start); dfree(e->route_cnt);
     dfree(e->order); dfree(e->order_meta); dfree(e->solo_list);
-    dfree(e->d_stats); dfree(e->retry_dbg); dfree(e->topk); dfree(e->usage);
+    dfree(e->d_stats); dfree(e->retry_dbg); dfree(e->topk); dfree(e->usage); dfree(e->digest); dfree(e->digest_fine);
     dfree(e->snap); dfree(e->put_heads); dfree(e->img_stage);
     dfree(e->s_key); dfree(e->s_permits); dfree(e->s_now); dfree(e->s_lim); dfree(e->s_op);
     dfree(e->s_allowed); dfree(e->s_remaining); dfree(e->s_tokens);
@@ -1477,6 +1481,92 @@ extern "C" int rl_top_consumers(rl_engine* e, uint16_t limiter, int64_t now_ns, 
     return RL_OK;
 }
 
+// ---------------------------------------------------------------- table digest
+// rl_digest.hip on the engine stream, under the census' rules (above): behind every batch
+// submitted before, the table as installed, no collect_status, nothing written but `out`.
+static_assert(RL_DIGEST_K_SW == kDigestKSw && RL_DIGEST_K_TB == kDigestKTb &&
+              RL_DIGEST_K_CACHE == kDigestKCache && RL_DIGEST_C1 == kDigestC1 &&
+              RL_DIGEST_C2 == kDigestC2, "digest constants");
+static_assert(sizeof(rl_bucket_digest) == 24 && sizeof(BucketDigest) == 24, "rl_bucket_digest layout");
+
+static bool digest_args_ok(const rl_engine* e, size_t limiter, uint32_t bucket_bits, uint32_t flags) {
+    if (limiter >= e->lims.size() || (flags & ~(uint32_t)RL_DIGEST_CACHE)) return false;
+    return bucket_bits <= (uint32_t)e->lims[limiter].dev.region_bits;
+}
+
+// Zeroes out[2^bucket_bits] (device) and launches the pass, both on the engine stream; for few
+// buckets the pass writes finer ones into e->digest_fine and a fold fills `out` (rl_digest.hip).
+static int digest_enqueue(rl_engine* e, size_t li, int64_t now_ns, uint32_t bucket_bits, uint32_t flags,
+                          BucketDigest* out) {
+    const HostLimiter& h = e->lims[li];
+    DigestArgs a{};
+    a.tab = (const Slot*)h.table;
+    a.n_regions = h.table_bytes / sizeof(Slot) / kRegionSlots;
+    a.L = h.dev;
+    a.now = floor_div_ms(now_ns);
+    a.bucket_bits = bucket_bits;
+    a.with_cache = (flags & RL_DIGEST_CACHE) ? 1u : 0u;
+    a.out = out;
+    a.per_cu = e->digest_per_cu;
+    if (a.n_regions != (1ULL << h.dev.region_bits)) return RL_E_INTERNAL;   // (buckets are region ranges)
+    const uint32_t fine = std::min<uint32_t>(kDigestFineBits, (uint32_t)h.dev.region_bits);
+    if (bucket_bits < fine) {
+        if (!e->digest_fine) {
+            int rc = dalloc(&e->digest_fine, (size_t)1 << kDigestFineBits);
+            if (rc != RL_OK) return rc;
+        }
+        a.bucket_bits = fine;
+        a.out = e->digest_fine;
+    }
+    HIP_OK(hipMemsetAsync(a.out, 0, sizeof(BucketDigest) << a.bucket_bits, e->stream));
+    HIP_OK(launch_digest(a, e->stream));
+    if (a.out != out) HIP_OK(launch_digest_fold(a.out, fine, out, bucket_bits, e->stream));
+    return RL_OK;
+}
+
+extern "C" int rl_limiter_digest_device(rl_engine* e, uint16_t limiter, int64_t now_ns,
+                                        uint32_t bucket_bits, uint32_t flags, rl_bucket_digest* out,
+                                        void* stream) {
+    if (!e || !out || ((uintptr_t)out & 7u)) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!digest_args_ok(e, limiter, bucket_bits, flags)) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    StreamJoin join(e->stream, (hipStream_t)stream);
+    HIP_OK(join.err);
+    int rc = digest_enqueue(e, limiter, now_ns, bucket_bits, flags, (BucketDigest*)out);
+    if (rc != RL_OK) return rc;
+    HIP_OK(join.finish());
+    return RL_OK;
+}
+
+extern "C" int rl_limiter_digest(rl_engine* e, uint16_t limiter, int64_t now_ns, uint32_t bucket_bits,
+                                 uint32_t flags, rl_bucket_digest* out, rl_bucket_digest* total) {
+    if (!e || !out) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!digest_args_ok(e, limiter, bucket_bits, flags)) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    const size_t nb = (size_t)1 << bucket_bits;
+    if (nb > e->digest_cap) {                         // (freeing waits for the device)
+        dfree(e->digest);
+        e->digest_cap = 0;
+        int rc = dalloc(&e->digest, nb);
+        if (rc != RL_OK) return rc;
+        e->digest_cap = nb;
+    }
+    int rc = digest_enqueue(e, limiter, now_ns, bucket_bits, flags, e->digest);
+    if (rc != RL_OK) return rc;
+    HIP_OK(hipMemcpyAsync(out, e->digest, nb * sizeof(BucketDigest), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    if (total) {
+        rl_bucket_digest t{0, 0, 0};
+        for (size_t b = 0; b < nb; ++b) {
+            t.entries += out[b].entries; t.sum += out[b].sum; t.xr ^= out[b].xr;
+        }
+        *total = t;
+    }
+    return RL_OK;
+}
+
 extern "C" int rl_batch_stats_get(rl_engine* e, rl_batch_stats* out) {
     if (!e || !out) return RL_E_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
@@ -1530,6 +1620,11 @@ extern "C" int rl_tune(rl_engine* e, const char* key, int64_t value) {
     if (std::strcmp(key, "unpermute_split") == 0) { e->un_split = (uint32_t)value; return RL_OK; }
     if (std::strcmp(key, "mid_xcd") == 0) { e->mid_xcd = value ? 1u : 0u; return RL_OK; }
     if (std::strcmp(key, "unpermute_per_cu") == 0) { e->un_per_cu = (uint32_t)value; return RL_OK; }
+    if (std::strcmp(key, "digest_per_cu") == 0) {      // k_digest workgroups per CU; 0 = default
+        if (value < 0 || value > 64) return RL_E_INVALID_ARG;
+        e->digest_per_cu = (uint32_t)value;
+        return RL_OK;
+    }
     if (std::strcmp(key, "debug_regions") == 0) { e->debug_regions = value != 0; return RL_OK; }
     if (std::strcmp(key, "wide_records") == 0) { e->force_wide = value != 0; return RL_OK; }
     if (std::strcmp(key, "stage_timing") == 0) {     // hipEvents around every stage on/off

@@ -591,6 +591,34 @@ hipError_t launch_usage_digits(const UsageScratch& sc, const Slot* table, uint64
                                const DevLimiter& L, int64_t now_ms, const UsageSel& sel, hipStream_t s);
 hipError_t launch_usage_compact(const UsageScratch& sc, const Slot* table, uint64_t n_slots,
                                 const DevLimiter& L, int64_t now_ms, const UsageSel& sel, hipStream_t s);
+// Table digest (rl_digest.hip; rl_limiter_digest(_device), include/rl_engine.h): one read-only
+// pass over the limiter's slots that folds a hash of every entry live at `now` into out[bucket],
+// bucket = the top bucket_bits of the slot's region index. The constants are ABI
+// (RL_DIGEST_*, asserted equal in rl_engine.cpp).
+constexpr uint64_t kDigestKSw = 0x9e3779b97f4a7c15ULL;
+constexpr uint64_t kDigestKTb = 0xc2b2ae3d27d4eb4fULL;
+constexpr uint64_t kDigestKCache = 0x165667b19e3779f9ULL;
+constexpr uint64_t kDigestC1 = 0xff51afd7ed558ccdULL;
+constexpr uint64_t kDigestC2 = 0xc4ceb9fe1a85ec53ULL;
+constexpr uint32_t kDigestPerCu = 8;             // workgroups per CU of the grid (rl_tune "digest_per_cu")
+struct BucketDigest { unsigned long long entries, sum, xr; };   // rl_bucket_digest
+struct DigestArgs {
+    const Slot* tab;
+    uint64_t n_regions;        // table_bytes / 32 / kRegionSlots = 2^L.region_bits
+    DevLimiter L;
+    int64_t now;               // ms
+    uint32_t bucket_bits;      // <= L.region_bits
+    uint32_t with_cache;       // RL_DIGEST_CACHE asked for (and L.cache_table != 0)
+    BucketDigest* out;         // [2^bucket_bits], zeroed on the stream before the launch
+    uint32_t per_cu;           // 0: kDigestPerCu
+};
+hipError_t launch_digest(const DigestArgs& a, hipStream_t s);
+// Fewer buckets than 2^kDigestFineBits are digested at kDigestFineBits (or the table's region
+// bits, if fewer) into a scratch of the engine and folded: out[b] = fine[b << d .. (b + 1) << d)
+// combined, d = fine_bits - bucket_bits (plain stores; `out` need not be zeroed).
+constexpr uint32_t kDigestFineBits = 10;
+hipError_t launch_digest_fold(const BucketDigest* fine, uint32_t fine_bits, BucketDigest* out,
+                              uint32_t bucket_bits, hipStream_t s);
 // skip (nullable): requests with skip[i] != 0 are neither counted nor placed; perm then holds
 // the others' stable owner order in its first sum(counts) entries
 hipError_t launch_owner_partition(const uint64_t* key, uint32_t n, uint32_t shard_count,

@@ -172,6 +172,78 @@ rl_shrink_report GpuEngine::shrink(uint16_t limiter, int64_t nowNanos, uint64_t 
     return r;
 }
 
+// Throws unless the limiter exists and its table has at least bucketBits region bits (so nothing
+// is sized by a bucketBits the engine would refuse); returns the table's region count.
+static uint64_t digestRegions(rl_engine* e, uint16_t limiter, uint32_t bucketBits, const char* what) {
+    uint64_t slots = 0;
+    const int st = rl_limiter_slots(e, limiter, &slots);
+    if (st == RL_E_INVALID_ARG) throw IllegalArgumentException(std::string(what) + ": " + rl_strerror(st));
+    if (st != RL_OK) throw StorageException(std::string(what) + ": " + rl_strerror(st), st);
+    const uint64_t regions = slots / RL_SNAPSHOT_MIN_CAP;    // 256 slots each
+    if (bucketBits > 63 || (regions >> bucketBits) == 0)
+        throw IllegalArgumentException(std::string(what) + ": bucketBits beyond the table's region bits");
+    return regions;
+}
+
+std::vector<rl_bucket_digest> GpuEngine::digest(uint16_t limiter, int64_t nowNanos, uint32_t bucketBits,
+                                                bool withCache) {
+    (void)digestRegions(e_, limiter, bucketBits, "digest");
+    std::vector<rl_bucket_digest> out((size_t)1 << bucketBits);
+    int st;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        st = rl_limiter_digest(e_, limiter, nowNanos, bucketBits, withCache ? RL_DIGEST_CACHE : 0u,
+                               out.data(), nullptr);
+    }
+    if (st == RL_E_INVALID_ARG) throw IllegalArgumentException(std::string("digest: ") + rl_strerror(st));
+    if (st != RL_OK) throw StorageException(std::string("digest: ") + rl_strerror(st), st);
+    return out;
+}
+
+size_t GpuEngine::snapshotChanged(uint16_t limiter, int64_t nowNanos, uint32_t bucketBits,
+                                  const std::vector<rl_bucket_digest>& previous,
+                                  std::vector<rl_bucket_digest>* current, size_t chunkImages,
+                                  const BucketSink& sink) {
+    (void)digestRegions(e_, limiter, bucketBits, "snapshotChanged");
+    if (!previous.empty() && previous.size() != (size_t)1 << bucketBits)
+        throw IllegalArgumentException("snapshotChanged: previous must hold 2^bucketBits digests (or none)");
+    const size_t nb = (size_t)1 << bucketBits;
+    const size_t cap = std::max<size_t>(chunkImages, RL_SNAPSHOT_MIN_CAP);
+    std::vector<rl_bucket_digest> now(nb);
+    std::vector<rl_key_image> buf(cap);
+    std::lock_guard<std::mutex> lk(mu_);             // no batch of this object between the calls
+    int st = rl_limiter_digest(e_, limiter, nowNanos, bucketBits, RL_DIGEST_CACHE, now.data(), nullptr);
+    if (st == RL_E_INVALID_ARG) throw IllegalArgumentException(std::string("snapshotChanged: ") + rl_strerror(st));
+    if (st != RL_OK) throw StorageException(std::string("snapshotChanged: ") + rl_strerror(st), st);
+    const uint64_t total0 = digestRegions(e_, limiter, bucketBits, "snapshotChanged");   // (held: as digested)
+    const uint64_t per = total0 >> bucketBits;               // regions per bucket (>= 1: the digest was taken)
+    size_t delivered = 0;
+    for (size_t b = 0; b < nb; ++b) {
+        if (!previous.empty() && previous[b].entries == now[b].entries && previous[b].sum == now[b].sum &&
+            previous[b].xr == now[b].xr)
+            continue;
+        uint64_t at = b * per;
+        const uint64_t end = at + per;
+        bool called = false;
+        while (at < end) {
+            size_t n = 0;
+            uint64_t done = 0, total = 0;
+            st = rl_snapshot_keys(e_, limiter, at, end - at, buf.data(), cap, &n, &done, &total);
+            if (st == RL_E_INVALID_ARG)
+                throw IllegalArgumentException(std::string("snapshotChanged: ") + rl_strerror(st));
+            if (st != RL_OK) throw StorageException(std::string("snapshotChanged: ") + rl_strerror(st), st);
+            if (total != total0 || done == 0)
+                throw StorageException("snapshotChanged: the table grew between two chunks", RL_E_INTERNAL);
+            if (n && sink) { sink((uint32_t)b, buf.data(), n); called = true; }
+            delivered += n;
+            at += done;
+        }
+        if (!called && sink) sink((uint32_t)b, buf.data(), 0);
+    }
+    if (current) *current = std::move(now);
+    return delivered;
+}
+
 GpuRateLimiter::GpuRateLimiter(std::shared_ptr<GpuEngine> engine, Algorithm algo,
                                const RateLimitConfig& cfg, Clock clock, int batchWindowMicros)
     : allowedRequests(algo == Algorithm::TokenBucket ? "ratelimiter.tokenbucket.allowed"
@@ -338,6 +410,19 @@ rl_usage GpuRateLimiter::usage() {
         ~Release() { lk.lock(); self->flushing_ = false; self->cv_.notify_all(); }
     } rel{this, lk};
     return engine_->usage(id_, now);
+}
+
+std::vector<rl_bucket_digest> GpuRateLimiter::digest(uint32_t bucketBits) {
+    std::unique_lock<std::mutex> lk(mu_);
+    cv_.wait(lk, [&] { return !flushing_; });
+    flushing_ = true;
+    const int64_t now = clock_();
+    lk.unlock();
+    struct Release {
+        GpuRateLimiter* self; std::unique_lock<std::mutex>& lk;
+        ~Release() { lk.lock(); self->flushing_ = false; self->cv_.notify_all(); }
+    } rel{this, lk};
+    return engine_->digest(id_, now, bucketBits);
 }
 
 rl_shrink_report GpuRateLimiter::compact() {

@@ -157,6 +157,26 @@ class GpuEngine {
     // exceed the now of any later request. IllegalArgumentException for an unknown limiter,
     // StorageException on a device error (the old table then still stands).
     rl_shrink_report shrink(uint16_t limiter, int64_t nowNanos, uint64_t minKeys = 0);
+    // rl_limiter_digest: the 2^bucketBits per-bucket fingerprints of the limiter's live state at
+    // nowNanos (with the rejecting local-cache entries unless withCache is false). Equal digests =
+    // the same Redis keyspace, whatever the tables' sizes. Read-only. IllegalArgumentException for
+    // an unknown limiter or bucketBits beyond the table's region bits.
+    std::vector<rl_bucket_digest> digest(uint16_t limiter, int64_t nowNanos, uint32_t bucketBits,
+                                         bool withCache = true);
+    // Incremental checkpoint: computes the digests (with cache entries) into *current (nullable)
+    // and, for every bucket whose digest differs from `previous` (empty: every bucket), delivers
+    // the bucket's images through rl_snapshot_keys over its region range, in chunks of at most
+    // chunkImages (at least RL_SNAPSHOT_MIN_CAP). `sink` is called at least once per changed
+    // bucket, with n == 0 if the bucket holds nothing now, so a checkpoint store replaces that
+    // bucket's chunk wholesale; an unchanged bucket is never delivered. Returns the images
+    // delivered. The engine is held for the whole call, as by snapshot(). Throws as snapshot():
+    // IllegalArgumentException for an unknown limiter, bucketBits too large or a `previous` whose
+    // length is not 2^bucketBits, StorageException if the table grew between two chunks.
+    using BucketSink = std::function<void(uint32_t bucket, const rl_key_image*, size_t)>;
+    size_t snapshotChanged(uint16_t limiter, int64_t nowNanos, uint32_t bucketBits,
+                           const std::vector<rl_bucket_digest>& previous,
+                           std::vector<rl_bucket_digest>* current, size_t chunkImages,
+                           const BucketSink& sink);
 
   private:
     rl_engine* e_ = nullptr;
@@ -204,6 +224,10 @@ class GpuRateLimiter : public RateLimiter {
     // keeps room for config().expectedKeys. Sees every tryAcquire of this object that has
     // returned; later decisions are unchanged.
     rl_shrink_report compact();
+    // The 2^bucketBits per-bucket fingerprints of this limiter's state at the clock's now (with
+    // its rejecting local-cache entries): compare with a replica's or a restored engine's, or
+    // keep them for GpuEngine::snapshotChanged. Read-only; sees every tryAcquire that has returned.
+    std::vector<rl_bucket_digest> digest(uint32_t bucketBits);
     // the reference's permits check (SlidingWindowRateLimiter.java:87-89,
     // TokenBucketRateLimiter.java:106-108): throws IllegalArgumentException for permits <= 0
     static void requirePositive(int permits);

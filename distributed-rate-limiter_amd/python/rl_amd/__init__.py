@@ -35,6 +35,10 @@ RETRY_ERROR = -3                      # RL_RETRY_ERROR (rl_router_retry_after: t
 TOP_KEYS_MAX, TOP_KEYS_CANDIDATES = 4096, 65536   # RL_TOP_KEYS_* (rl_top_keys)
 USAGE_BINS, USAGE_CANDIDATES = 16, 65536   # RL_USAGE_* (rl_limiter_usage, rl_top_consumers)
 MOVE_KEYS_MAX = 8192                       # RL_MOVE_KEYS_MAX: keys per rl_copy_keys / rl_drop_keys
+DIGEST_CACHE = 1                           # RL_DIGEST_CACHE: also digest the rejecting local-cache entries
+# RL_DIGEST_K_SW / _K_TB / _K_CACHE and RL_DIGEST_C1 / _C2 (include/rl_engine.h): the entry hash
+DIGEST_K = (0x9E3779B97F4A7C15, 0xC2B2AE3D27D4EB4F, 0x165667B19E3779F9)
+DIGEST_C1, DIGEST_C2 = 0xFF51AFD7ED558CCD, 0xC4CEB9FE1A85EC53
 SNAPSHOT_MIN_CAP = 256                     # RL_SNAPSHOT_MIN_CAP: a snapshot cap that always makes progress
 SHRINK_FILL_MAX, SHRINK_LEVELS = 104, 24   # RL_SHRINK_* (rl_shrink_plan, rl_shrink_limiter)
 PUT_REJECT_ORDER, PUT_REJECT_LIMITER = 1, 2   # `rejected` bits of rl_put_keys_device's header
@@ -61,6 +65,7 @@ EXPORTS = [
     "rl_retry_after", "rl_retry_after_device",
     "rl_top_keys", "rl_top_keys_device", "rl_router_plan_directory_sampled",
     "rl_limiter_usage", "rl_top_consumers",
+    "rl_limiter_digest", "rl_limiter_digest_device",
     "rl_copy_keys", "rl_drop_keys", "rl_put_keys",
     "rl_router_replan_directory", "rl_router_replan_directory_sampled",
     "rl_snapshot_keys", "rl_snapshot_keys_device", "rl_put_keys_device", "rl_restore_keys",
@@ -113,6 +118,16 @@ class Usage(ctypes.Structure):
                                                  "exhausted_keys", "cache_blocked",
                                                  "used_permits")] + \
                [("hist", ctypes.c_uint64 * USAGE_BINS)]
+
+
+class BucketDigest(ctypes.Structure):
+    """rl_bucket_digest (include/rl_engine.h): count, wrapping sum and xor of one bucket's entry
+    hashes."""
+    _fields_ = [("entries", ctypes.c_uint64), ("sum", ctypes.c_uint64), ("xr", ctypes.c_uint64)]
+
+
+DIGEST_DTYPE = np.dtype([("entries", "<u8"), ("sum", "<u8"), ("xr", "<u8")])
+assert DIGEST_DTYPE.itemsize == ctypes.sizeof(BucketDigest) == 24
 
 
 class ShrinkReport(ctypes.Structure):
@@ -226,6 +241,8 @@ def lib():
     L.rl_limiter_usage.argtypes = [vp, u16, i64, ctypes.POINTER(Usage)]
     L.rl_top_consumers.argtypes = [vp, u16, i64, u32, i64, vp, vp, ctypes.POINTER(sz),
                                    ctypes.POINTER(ctypes.c_uint64)]
+    L.rl_limiter_digest.argtypes = [vp, u16, i64, u32, u32, vp, ctypes.POINTER(BucketDigest)]
+    L.rl_limiter_digest_device.argtypes = [vp, u16, i64, u32, u32, vp, vp]
     L.rl_owner_of_engine.restype = u32
     L.rl_copy_keys.argtypes = [vp, sz, vp, vp, sz, ctypes.POINTER(sz)]
     L.rl_drop_keys.argtypes = [vp, sz, vp, ctypes.POINTER(ctypes.c_uint64)]
@@ -279,6 +296,50 @@ def mix64(x):
         x = x * np.uint64(0x94D049BB133111EB)
         x = x ^ (x >> np.uint64(31))
     return x
+
+
+def _rotl64(x, r):
+    return (x << np.uint64(r)) | (x >> np.uint64(64 - r))
+
+
+def digest_model(entries, cache_entries, shard_count, bucket_bits):
+    """rl_limiter_digest restated in numpy from its definition in include/rl_engine.h, for one
+    limiter: `entries` are tuples in PyOracle.keyspace() order (limiter, key_hash, kind,
+    window_start, count, tokens, last_refill, expire_at) - the limiter field is ignored -,
+    `cache_entries` are (key_hash, x) pairs of the cache words that reject. Returns a
+    DIGEST_DTYPE array of 2^bucket_bits buckets. Not used by the engine."""
+    entries, cache_entries = list(entries), list(cache_entries)
+    n, m = len(entries), len(cache_entries)
+    key = np.zeros(n + m, np.uint64)
+    kind = np.zeros(n + m, np.int64)
+    f = np.zeros((3, n + m), np.uint64)
+    u64 = lambda v: int(v) & 0xFFFFFFFFFFFFFFFF  # noqa: E731
+    for i, (_, kh, kd, w0, cnt, tok, last, exp) in enumerate(entries):
+        key[i], kind[i] = u64(kh), 1 if kd else 0
+        if kd:
+            f[0, i] = int(np.array([tok], "<f8").view("<u8")[0])
+            f[1, i] = u64(last)
+        else:
+            f[0, i], f[1, i] = u64(w0), u64(cnt)
+        f[2, i] = u64(exp)
+    for i, (kh, x) in enumerate(cache_entries):
+        key[n + i], kind[n + i], f[0, n + i] = u64(kh), 2, u64(x)
+    tag = mix64(key)
+    with np.errstate(over="ignore"):
+        u = tag + np.array(DIGEST_K, np.uint64)[kind]
+        u = (u ^ f[0]) * np.uint64(DIGEST_C1)
+        u = (u ^ _rotl64(f[1], 23)) * np.uint64(DIGEST_C2)
+        u = u ^ _rotl64(f[2], 47)
+        h = mix64(u)
+    s = int(shard_count).bit_length() - 1 if shard_count > 1 else 0
+    g = int(bucket_bits)
+    bucket = ((tag << np.uint64(s)) >> np.uint64(64 - g)).astype(np.int64) if g else np.zeros(n + m, np.int64)
+    out = np.zeros(1 << g, DIGEST_DTYPE)
+    with np.errstate(over="ignore"):
+        np.add.at(out["entries"], bucket, np.uint64(1))
+        np.add.at(out["sum"], bucket, h)
+        np.bitwise_xor.at(out["xr"], bucket, h)
+    return out
 
 
 def key_hash(key: str) -> int:
@@ -511,6 +572,30 @@ class Engine:
         if st != RL_OK:
             raise RlError(st, "rl_top_consumers")
         return keys[:n_out.value], used[:n_out.value], n_match.value
+
+    def limiter_digest(self, limiter, now_ns, bucket_bits, cache=True):
+        """Per-bucket fingerprints of a limiter's live state at now_ns (rl_limiter_digest), with
+        the rejecting local-cache entries unless `cache` is false. Returns (a DIGEST_DTYPE array
+        of 2^bucket_bits buckets, the total over them as an (entries, sum, xr) tuple). Read-only."""
+        bits, slots = int(bucket_bits), ctypes.c_uint64(0)
+        known = self._L.rl_limiter_slots(self._h, int(limiter), ctypes.byref(slots)) == RL_OK
+        fits = known and 0 <= bits < 64 and (slots.value // REGION_SLOTS) >> bits   # (else: refused below)
+        out = np.zeros(1 << bits if fits else 1, DIGEST_DTYPE)
+        tot = BucketDigest()
+        st = self._L.rl_limiter_digest(self._h, int(limiter), int(now_ns), int(bucket_bits),
+                                       DIGEST_CACHE if cache else 0, _p(out), ctypes.byref(tot))
+        if st != RL_OK:
+            raise RlError(st, "rl_limiter_digest")
+        return out, (tot.entries, tot.sum, tot.xr)
+
+    def limiter_digest_device(self, limiter, now_ns, bucket_bits, out, cache=True, stream=None):
+        """rl_limiter_digest_device: `out` is a device buffer of 2^bucket_bits x 24 bytes (a torch
+        tensor or a raw pointer, 8-byte aligned); asynchronous, ordered behind the batches
+        submitted before it."""
+        st = self._L.rl_limiter_digest_device(self._h, int(limiter), int(now_ns), int(bucket_bits),
+                                              DIGEST_CACHE if cache else 0, _p(out), _p(stream))
+        if st != RL_OK:
+            raise RlError(st, "rl_limiter_digest_device")
 
     def export_state(self, now_ns):
         """Live state at now_ns in the Redis layout: a STATE_DTYPE array (rl_export_state)."""

@@ -582,6 +582,87 @@ int  rl_limiter_usage(rl_engine* e, uint16_t limiter, int64_t now_ns, rl_usage* 
 int  rl_top_consumers(rl_engine* e, uint16_t limiter, int64_t now_ns, uint32_t k, int64_t min_used,
                       uint64_t* key_hash, int64_t* used, size_t* n_out, uint64_t* n_match);
 
+/* ---- table digest: per-bucket fingerprints of a limiter's live state ---------------
+ * What DEBUG DIGEST answers for the reference's Redis, per range of the table: is this limiter's
+ * state the same as that one's (a replica, a restore, the table after a re-plan or a shrink), and
+ * if not, in which buckets do they differ. One read-only pass over the limiter's slots (32 B each,
+ * + 8 B of cache word with RL_DIGEST_CACHE), no sort, no per-slot atomic, a few KB back
+ * (rl_export_state moves 56 B per Redis key and sorts on the host).
+ *
+ * The digest is taken over the LOGICAL state at now = floorDiv(now_ns, 1e6), not over the stored
+ * bits, as a multiset of entries:
+ *   - every entry rl_export_state(now_ns) would emit for this limiter:
+ *       sliding window  one per live bucket "rl:<key>:<W>":  kind SW, fields
+ *                       (f1, f2, f3) = (window_start_ms, count, expire_at_ms)
+ *       token bucket    one per live hash "tb:<key>":        kind TB, fields
+ *                       (f1, f2, f3) = (the 64 bits of `tokens` as stored, last_refill_ms,
+ *                       expire_at_ms)   (so +0.0 and -0.0 balances differ)
+ *   - with RL_DIGEST_CACHE, and only if the limiter has a local cache: one entry of kind CACHE,
+ *     fields (x, 0, 0), for every key whose cache word x rejects at now (x != 0 && now < x, the
+ *     cache_blocked rule of rl_usage; x is the millisecond at which the entry stops rejecting =
+ *     write time + localCacheTtl, kept only for a cached value >= maxPermits).
+ * Tombstones, free slots and state dead at now contribute nothing, so the digest does not change
+ * under rl_grow_limiter, rl_sweep_expired, rl_shrink_limiter, snapshot / restore, migration or
+ * slot placement, and a caller can recompute it from rl_export_state output or from the
+ * reference's keyspace.
+ *
+ * Entry hash. All arithmetic is uint64 and wrapping; signed fields are taken as their two's
+ * complement bits; rotl is a 64-bit left rotation; mix64 is the engine's key mixer, the
+ * splitmix64 finaliser
+ *     mix64(x):  x ^= x >> 30;  x *= 0xbf58476d1ce4e5b9;  x ^= x >> 27;  x *= 0x94d049bb133111eb;
+ *                x ^= x >> 31
+ * and tag = mix64(key_hash):
+ *     u = tag + K[kind];  u = (u ^ f1) * C1;  u = (u ^ rotl(f2, 23)) * C2;  u ^= rotl(f3, 47);
+ *     H = mix64(u)
+ *   K[SW] = RL_DIGEST_K_SW, K[TB] = RL_DIGEST_K_TB, K[CACHE] = RL_DIGEST_K_CACHE,
+ *   C1 = RL_DIGEST_C1, C2 = RL_DIGEST_C2 (all odd, below; fixed: part of the ABI).
+ * The limiter id is not hashed: two engines' limiters compare whatever their ids are.
+ *
+ * Bucket of an entry: bucket = the top bucket_bits bits of tag below the shard bits
+ * (bucket_bits == 0: one bucket). A region is the top region_bits of those same bits, so bucket
+ * b is the regions [b << (k - g), (b + 1) << (k - g)) of a table with k region bits, for every
+ * table with k >= g = bucket_bits: tables of different sizes that hold the same keys give the
+ * same digests, and a bucket is a region range rl_snapshot_keys takes. Every table has at least
+ * 8 regions (k >= 3). out[b] = { entries digested, sum of H mod 2^64, xor of H } over bucket b's
+ * entries; `total` (nullable) = the same over all buckets.
+ *
+ * What equality means:
+ *   - Equal digests at one now mean, up to a 2^-64-class collision, that the two limiters hold
+ *     the same Redis keyspace at now (and the same rejecting cache entries with RL_DIGEST_CACHE).
+ *   - A digest taken at now_1 that equals one taken earlier at now_0 <= now_1 means the bucket's
+ *     live entries are the same set: every key the table has dropped since was dead at now_1. So
+ *     a checkpoint chunk of that bucket taken at now_0 still restores to state that decides
+ *     identically from now_1 on.
+ *   - Expiry alone can make digests differ; the cost is only a chunk snapshotted again.
+ *
+ * Both calls only read: no limiter state, cache word, batch statistic, and not the status
+ * rl_last_status reports, which they do not collect either. They read the table as installed (a
+ * growth nobody has collected is not applied) on the engine's stream behind every batch submitted
+ * before them (RL_OPT_PIPELINE included). The host form synchronises; the device form is enqueued
+ * (joined with `stream` as the other *_device calls) and returns argument or launch status only;
+ * all 2^bucket_bits entries of `out` are written on the stream. RL_E_INVALID_ARG, before any device call and with the
+ * outputs untouched: a null engine (checked first), an unknown limiter, a null out, flag bits
+ * other than RL_DIGEST_CACHE, bucket_bits greater than the limiter's current region bits
+ * (log2(rl_limiter_slots / 256)), a device out that is not 8-byte aligned. Multi-GPU: an engine
+ * digests its own shard; buckets lie below the shard bits, so shard s of one deployment compares
+ * with shard s of another, and the shards' `entries` add up to the unsharded table's. */
+#define RL_DIGEST_CACHE 0x1u        /* also digest the local-cache entries that reject at now */
+#define RL_DIGEST_K_SW    0x9e3779b97f4a7c15ULL
+#define RL_DIGEST_K_TB    0xc2b2ae3d27d4eb4fULL
+#define RL_DIGEST_K_CACHE 0x165667b19e3779f9ULL
+#define RL_DIGEST_C1      0xff51afd7ed558ccdULL
+#define RL_DIGEST_C2      0xc4ceb9fe1a85ec53ULL
+typedef struct rl_bucket_digest {   /* 24 bytes */
+    uint64_t entries;               /* entries digested in this bucket */
+    uint64_t sum;                   /* sum of H(entry) mod 2^64 */
+    uint64_t xr;                    /* xor of H(entry) */
+} rl_bucket_digest;
+int  rl_limiter_digest(rl_engine* e, uint16_t limiter, int64_t now_ns, uint32_t bucket_bits,
+                       uint32_t flags, rl_bucket_digest* out /* HOST [2^bucket_bits] */,
+                       rl_bucket_digest* total /* nullable: all buckets combined */);
+int  rl_limiter_digest_device(rl_engine* e, uint16_t limiter, int64_t now_ns, uint32_t bucket_bits,
+                              uint32_t flags, rl_bucket_digest* out /* DEVICE */, void* stream);
+
 /* ---- multi-GPU routing helpers (device buffers, engine stream) ------------
  * owner(key_hash) is the shard that holds the key's state. rl_route_partition
  * stably partitions a batch by owner: perm[j] = source index of the j-th request
