@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/rl_engine.h"
+#include "rl_keys.hpp"
 #include "rl_launch.hpp"
 #include "rl_shrink.hpp"
 #include "rl_snapshot.hpp"
@@ -205,6 +206,15 @@ struct rl_engine {
     size_t put_heads_cap = 0;
     KeyImage* img_stage = nullptr;          // [img_stage_cap] images of rl_snapshot_keys / rl_restore_keys
     size_t img_stage_cap = 0;
+    // string-key staging of rl_hash_keys / rl_execute_batch_keys, on first use
+    size_t key_stage_bytes = (size_t)4 << 20;   // rl_tune("key_stage_bytes"): the blob stage's size
+    uint8_t* ks_blob = nullptr;             // [ks_blob_cap] one chunk of key bytes
+    size_t ks_blob_cap = 0;
+    uint64_t* ks_off = nullptr;             // [ks_keys_cap + 1] offsets
+    uint64_t* ks_hash = nullptr;            // [ks_keys_cap] rl_hash_keys' hashes
+    unsigned long long* ks_hdr = nullptr;   // [2] the chunks' headers (the host checked the offsets)
+    size_t ks_keys_cap = 0;
+    bool keys_direct = false;               // rl_tune("keys_direct"): k_hash_keys' direct path only
 };
 
 #define HIP_OK(x)                                                      \
@@ -408,6 +418,7 @@ extern "C" void rl_destroy(rl_engine* e) {
     dfree(e->order); dfree(e->order_meta); dfree(e->solo_list);
     dfree(e->d_stats); dfree(e->retry_dbg); dfree(e->topk); dfree(e->usage); dfree(e->digest); dfree(e->digest_fine);
     dfree(e->snap); dfree(e->put_heads); dfree(e->img_stage);
+    dfree(e->ks_blob); dfree(e->ks_off); dfree(e->ks_hash); dfree(e->ks_hdr);
     dfree(e->s_key); dfree(e->s_permits); dfree(e->s_now); dfree(e->s_lim); dfree(e->s_op);
     dfree(e->s_allowed); dfree(e->s_remaining); dfree(e->s_tokens);
     dfree(e->route_scratch); dfree(e->route_counts); dfree(e->d_dir);
@@ -1074,13 +1085,14 @@ static int ensure_staging(rl_engine* e, size_t n) {
     return RL_OK;
 }
 
-// The host-buffer calls' requests into the staging arrays (limiter, op_or_skip: nullable).
+// The host-buffer calls' requests into the staging arrays (limiter, op_or_skip: nullable; key
+// null: s_key is filled by the caller, rl_execute_batch_keys).
 static int stage_requests(rl_engine* e, size_t n, const uint64_t* key, const int32_t* permits,
                           const int64_t* now_ns, const uint16_t* limiter, const uint8_t* op_or_skip) {
     const int rc = ensure_staging(e, n);
     if (rc != RL_OK) return rc;
     hipStream_t s = e->stream;
-    HIP_OK(hipMemcpyAsync(e->s_key, key, n * 8, hipMemcpyHostToDevice, s));
+    if (key) HIP_OK(hipMemcpyAsync(e->s_key, key, n * 8, hipMemcpyHostToDevice, s));
     HIP_OK(hipMemcpyAsync(e->s_permits, permits, n * 4, hipMemcpyHostToDevice, s));
     HIP_OK(hipMemcpyAsync(e->s_now, now_ns, n * 8, hipMemcpyHostToDevice, s));
     if (limiter) HIP_OK(hipMemcpyAsync(e->s_lim, limiter, n * 2, hipMemcpyHostToDevice, s));
@@ -1088,22 +1100,14 @@ static int stage_requests(rl_engine* e, size_t n, const uint64_t* key, const int
     return RL_OK;
 }
 
-extern "C" int rl_execute_batch(rl_engine* e, size_t n, const uint64_t* key,
-                                const int32_t* permits, const int64_t* now_ns,
-                                const uint16_t* limiter, const uint8_t* op, uint8_t* allowed,
-                                int64_t* remaining, double* tokens_after) {
-    if (!e) return RL_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (n > e->opts.max_batch) return RL_E_TOO_LARGE;
-    if (n == 0) return RL_OK;
-    if (!key || !permits || !now_ns || !allowed || !remaining) return RL_E_INVALID_ARG;
-    (void)hipSetDevice(e->device);
-    int rc = stage_requests(e, n, key, permits, now_ns, limiter, op);
-    if (rc != RL_OK) return rc;
+// The staged batch (stage_requests) run, collected and copied back: the body of the host-buffer
+// batch calls.
+static int run_staged_batch(rl_engine* e, size_t n, bool limiter, bool op, uint8_t* allowed,
+                            int64_t* remaining, double* tokens_after) {
     hipStream_t s = e->stream;
-    rc = run_batch_device(e, n, e->s_key, e->s_permits, e->s_now, limiter ? e->s_lim : nullptr,
-                          op ? e->s_op : nullptr, e->s_allowed, e->s_remaining,
-                          tokens_after ? e->s_tokens : nullptr);
+    int rc = run_batch_device(e, n, e->s_key, e->s_permits, e->s_now, limiter ? e->s_lim : nullptr,
+                              op ? e->s_op : nullptr, e->s_allowed, e->s_remaining,
+                              tokens_after ? e->s_tokens : nullptr);
     if (rc != RL_OK) { (void)hipStreamSynchronize(s); return rc; }
     rc = collect_status(e);
     if (rc == RL_E_INVALID_ARG && e->h_ctl->span_overflow && !e->force_wide) {
@@ -1122,6 +1126,21 @@ extern "C" int rl_execute_batch(rl_engine* e, size_t n, const uint64_t* key,
     if (tokens_after) HIP_OK(hipMemcpyAsync(tokens_after, e->s_tokens, n * 8, hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
     return rc;
+}
+
+extern "C" int rl_execute_batch(rl_engine* e, size_t n, const uint64_t* key,
+                                const int32_t* permits, const int64_t* now_ns,
+                                const uint16_t* limiter, const uint8_t* op, uint8_t* allowed,
+                                int64_t* remaining, double* tokens_after) {
+    if (!e) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (n > e->opts.max_batch) return RL_E_TOO_LARGE;
+    if (n == 0) return RL_OK;
+    if (!key || !permits || !now_ns || !allowed || !remaining) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    int rc = stage_requests(e, n, key, permits, now_ns, limiter, op);
+    if (rc != RL_OK) return rc;
+    return run_staged_batch(e, n, limiter != nullptr, op != nullptr, allowed, remaining, tokens_after);
 }
 
 // Page-lock a caller's host buffer so the host-buffer entry points DMA it directly instead
@@ -1481,6 +1500,136 @@ extern "C" int rl_top_consumers(rl_engine* e, uint16_t limiter, int64_t now_ns, 
     return RL_OK;
 }
 
+// ---------------------------------------------------------------- string keys
+// rl_keys.hip on the engine stream. The hash calls touch no limiter table, batch scratch,
+// d_stats, d_ctl or the status bookkeeping; rl_execute_batch_keys hashes into s_key and then
+// runs the batch as rl_execute_batch does.
+static_assert(RL_KEY_MAX_BYTES == kKeyMaxBytes, "key length limit");
+constexpr uint64_t kKeysMaxN = 1ULL << 31;
+
+extern "C" uint64_t rl_key_hash(const void* bytes, size_t len) {
+    const unsigned char* b = (const unsigned char*)bytes;
+    uint64_t h = kFnvOffset;
+    for (size_t i = 0; i < len; ++i) h = (h ^ b[i]) * kFnvPrime;
+    return mix64(h);
+}
+
+static int hash_keys_enqueue(rl_engine* e, size_t n, const uint8_t* bytes, uint64_t bytes_len,
+                             const uint64_t* off, uint64_t bias, uint64_t* out, unsigned long long* hdr) {
+    HIP_OK(hipMemsetAsync(hdr, 0, 2 * sizeof(uint64_t), e->stream));
+    KeysArgs a{};
+    a.bytes = bytes; a.bytes_len = bytes_len; a.off = off; a.bias = bias; a.n = n; a.out = out;
+    a.hdr = hdr; a.direct = e->keys_direct ? 1u : 0u;
+    HIP_OK(launch_hash_keys(a, e->stream));
+    return RL_OK;
+}
+
+extern "C" int rl_hash_keys_device(rl_engine* e, size_t n, const uint8_t* key_bytes, size_t key_bytes_len,
+                                   const uint64_t* key_off, uint64_t* key_hash, uint64_t* hdr,
+                                   void* stream) {
+    if (!e) return RL_E_INVALID_ARG;
+    if ((n && (!key_off || !key_hash)) || !hdr || (key_bytes_len && !key_bytes)) return RL_E_INVALID_ARG;
+    if (((uintptr_t)key_off | (uintptr_t)key_hash | (uintptr_t)hdr) & 7u) return RL_E_INVALID_ARG;
+    if ((uint64_t)n > kKeysMaxN) return RL_E_TOO_LARGE;
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipSetDevice(e->device);
+    StreamJoin join(e->stream, (hipStream_t)stream);
+    HIP_OK(join.err);
+    const int rc = hash_keys_enqueue(e, n, key_bytes, key_bytes_len, key_off, 0, key_hash,
+                                     (unsigned long long*)hdr);
+    HIP_OK(join.finish());
+    return rc;
+}
+
+// The arguments of the two host forms; every offset is checked before any device call.
+static bool keys_host_args_ok(size_t n, const uint8_t* key_bytes, size_t key_bytes_len, const uint64_t* key_off) {
+    if (n == 0) return true;
+    if (!key_off || (key_bytes_len && !key_bytes) || ((uintptr_t)key_off & 7u)) return false;
+    return keys_first_malformed(key_off, n, key_bytes_len) == n;
+}
+
+// The blob stage and room for `keys` offsets (+ 1) and hashes.
+static int ensure_key_stage(rl_engine* e, size_t keys) {
+    if (e->ks_blob_cap != e->key_stage_bytes) {
+        dfree(e->ks_blob);
+        e->ks_blob_cap = 0;
+        int rc = dalloc(&e->ks_blob, e->key_stage_bytes);
+        if (rc != RL_OK) return rc;
+        e->ks_blob_cap = e->key_stage_bytes;
+    }
+    if (!e->ks_hdr) {
+        int rc = dalloc(&e->ks_hdr, 2);
+        if (rc != RL_OK) return rc;
+    }
+    if (keys > e->ks_keys_cap) {
+        dfree(e->ks_off); dfree(e->ks_hash);
+        e->ks_keys_cap = 0;
+        int rc = dalloc(&e->ks_off, keys + 1);
+        if (rc == RL_OK) rc = dalloc(&e->ks_hash, keys);
+        if (rc != RL_OK) return rc;
+        e->ks_keys_cap = keys;
+    }
+    return RL_OK;
+}
+
+// One staged chunk: keys [at, at + m) of the host batch hashed into out[0, m) (device). The
+// chunk's bytes go through ks_blob; `d_off` holds the chunk's m + 1 offsets on the device.
+static int hash_keys_chunk(rl_engine* e, const uint8_t* key_bytes, const uint64_t* key_off, size_t at,
+                           size_t m, const uint64_t* d_off, uint64_t* out) {
+    const uint64_t base = key_off[at], bytes = key_off[at + m] - base;
+    if (bytes) HIP_OK(hipMemcpyAsync(e->ks_blob, key_bytes + base, bytes, hipMemcpyHostToDevice, e->stream));
+    return hash_keys_enqueue(e, m, e->ks_blob, bytes, d_off, base, out, e->ks_hdr);
+}
+
+extern "C" int rl_hash_keys(rl_engine* e, size_t n, const uint8_t* key_bytes, size_t key_bytes_len,
+                            const uint64_t* key_off, uint64_t* key_hash) {
+    if (!e) return RL_E_INVALID_ARG;
+    if ((n && !key_hash) || !keys_host_args_ok(n, key_bytes, key_bytes_len, key_off)) return RL_E_INVALID_ARG;
+    if (n == 0) return RL_OK;
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipSetDevice(e->device);
+    const size_t max_keys = (size_t)std::min<uint64_t>(e->opts.max_batch, n);
+    int rc = ensure_key_stage(e, max_keys);
+    if (rc != RL_OK) return rc;
+    hipStream_t s = e->stream;
+    for (size_t at = 0; at < n;) {
+        const size_t m = keys_chunk(key_off, n, at, max_keys, e->key_stage_bytes);
+        HIP_OK(hipMemcpyAsync(e->ks_off, key_off + at, (m + 1) * 8, hipMemcpyHostToDevice, s));
+        rc = hash_keys_chunk(e, key_bytes, key_off, at, m, e->ks_off, e->ks_hash);
+        if (rc != RL_OK) { (void)hipStreamSynchronize(s); return rc; }
+        HIP_OK(hipMemcpyAsync(key_hash + at, e->ks_hash, m * 8, hipMemcpyDeviceToHost, s));
+        at += m;
+    }
+    HIP_OK(hipStreamSynchronize(s));
+    return RL_OK;
+}
+
+extern "C" int rl_execute_batch_keys(rl_engine* e, size_t n, const uint8_t* key_bytes, size_t key_bytes_len,
+                                     const uint64_t* key_off, const int32_t* permits, const int64_t* now_ns,
+                                     const uint16_t* limiter, const uint8_t* op, uint8_t* allowed,
+                                     int64_t* remaining, double* tokens_after, uint64_t* key_hash_out) {
+    if (!e) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (n > e->opts.max_batch) return RL_E_TOO_LARGE;
+    if (n == 0) return RL_OK;
+    if (!permits || !now_ns || !allowed || !remaining) return RL_E_INVALID_ARG;
+    if (!keys_host_args_ok(n, key_bytes, key_bytes_len, key_off)) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    int rc = ensure_key_stage(e, n);
+    if (rc == RL_OK) rc = stage_requests(e, n, nullptr, permits, now_ns, limiter, op);
+    if (rc != RL_OK) return rc;
+    hipStream_t s = e->stream;
+    HIP_OK(hipMemcpyAsync(e->ks_off, key_off, (n + 1) * 8, hipMemcpyHostToDevice, s));
+    for (size_t at = 0; at < n;) {                     // byte chunks, hashed straight into s_key
+        const size_t m = keys_chunk(key_off, n, at, n, e->key_stage_bytes);
+        rc = hash_keys_chunk(e, key_bytes, key_off, at, m, e->ks_off + at, e->s_key + at);
+        if (rc != RL_OK) { (void)hipStreamSynchronize(s); return rc; }
+        at += m;
+    }
+    if (key_hash_out) HIP_OK(hipMemcpyAsync(key_hash_out, e->s_key, n * 8, hipMemcpyDeviceToHost, s));
+    return run_staged_batch(e, n, limiter != nullptr, op != nullptr, allowed, remaining, tokens_after);
+}
+
 // ---------------------------------------------------------------- table digest
 // rl_digest.hip on the engine stream, under the census' rules (above): behind every batch
 // submitted before, the table as installed, no collect_status, nothing written but `out`.
@@ -1625,6 +1774,12 @@ extern "C" int rl_tune(rl_engine* e, const char* key, int64_t value) {
         e->digest_per_cu = (uint32_t)value;
         return RL_OK;
     }
+    if (std::strcmp(key, "key_stage_bytes") == 0) {    // blob stage of the string-key host forms
+        if (value < (int64_t)kKeyMaxBytes || value > ((int64_t)1 << 32)) return RL_E_INVALID_ARG;
+        e->key_stage_bytes = (size_t)value;            // (allocated by the next call that stages)
+        return RL_OK;
+    }
+    if (std::strcmp(key, "keys_direct") == 0) { e->keys_direct = value != 0; return RL_OK; }
     if (std::strcmp(key, "debug_regions") == 0) { e->debug_regions = value != 0; return RL_OK; }
     if (std::strcmp(key, "wide_records") == 0) { e->force_wide = value != 0; return RL_OK; }
     if (std::strcmp(key, "stage_timing") == 0) {     // hipEvents around every stage on/off

@@ -619,6 +619,21 @@ hipError_t launch_digest(const DigestArgs& a, hipStream_t s);
 constexpr uint32_t kDigestFineBits = 10;
 hipError_t launch_digest_fold(const BucketDigest* fine, uint32_t fine_bits, BucketDigest* out,
                               uint32_t bucket_bits, hipStream_t s);
+// String keys hashed on the device (rl_keys.hip; rl_hash_keys(_device), rl_execute_batch_keys,
+// include/rl_engine.h): out[i] = rl_key_hash of the bytes [off[i] - bias, off[i + 1] - bias) of
+// `bytes`, or 0 for a key that is not well-formed within bytes_len (rl_keys.hpp), which is
+// counted into hdr[0]; hdr[1] = n. hdr[0] is zeroed on the stream before the launch.
+struct KeysArgs {
+    const uint8_t* bytes;      // any alignment; null only with bytes_len == 0
+    uint64_t bytes_len;
+    const uint64_t* off;       // [n + 1]
+    uint64_t bias;             // the offset of bytes[0] (a staged chunk's first byte; else 0)
+    uint64_t n;                // <= 2^31
+    uint64_t* out;             // [n]
+    unsigned long long* hdr;   // [2]
+    uint32_t direct;           // rl_tune "keys_direct": every workgroup takes the direct path
+};
+hipError_t launch_hash_keys(const KeysArgs& a, hipStream_t s);
 // skip (nullable): requests with skip[i] != 0 are neither counted nor placed; perm then holds
 // the others' stable owner order in its first sum(counts) entries
 hipError_t launch_owner_partition(const uint64_t* key, uint32_t n, uint32_t shard_count,

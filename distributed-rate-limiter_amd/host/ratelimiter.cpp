@@ -6,16 +6,13 @@
 
 namespace ratelimiter {
 
-uint64_t keyHash(const std::string& key) {
-    uint64_t h = 0xcbf29ce484222325ULL;                 // FNV-1a 64
-    for (unsigned char c : key) {
-        h ^= c;
-        h *= 0x100000001b3ULL;
-    }
-    h ^= h >> 30; h *= 0xbf58476d1ce4e5b9ULL;           // splitmix64 finaliser
-    h ^= h >> 27; h *= 0x94d049bb133111ebULL;
-    h ^= h >> 31;
-    return h;
+uint64_t keyHash(const std::string& key) { return rl_key_hash(key.data(), key.size()); }
+
+void KeyBatch::add(std::string_view key) {
+    if (key.size() > RL_KEY_MAX_BYTES)
+        throw IllegalArgumentException("KeyBatch: key longer than RL_KEY_MAX_BYTES");
+    bytes_.insert(bytes_.end(), key.begin(), key.end());
+    off_.push_back(bytes_.size());
 }
 
 int64_t systemNanos() {
@@ -64,6 +61,31 @@ int GpuEngine::executeBatch(size_t n, const uint64_t* key, const int32_t* permit
     rl_batch_stats bs{};
     if (cacheHits) *cacheHits = rl_batch_stats_get(e_, &bs) == RL_OK ? bs.cache_hits : 0;
     return st;
+}
+
+int GpuEngine::executeBatchKeys(const KeyBatch& keys, const int32_t* permits, const int64_t* now,
+                                const uint16_t* limiter, const uint8_t* op, uint8_t* allowed,
+                                int64_t* remaining, uint64_t* keyHashOut, uint64_t* cacheHits) {
+    std::lock_guard<std::mutex> lk(mu_);
+    const int st = rl_execute_batch_keys(e_, keys.size(), keys.bytes().data(), keys.bytes().size(),
+                                         keys.offsets().data(), permits, now, limiter, op, allowed,
+                                         remaining, nullptr, keyHashOut);
+    rl_batch_stats bs{};
+    if (cacheHits) *cacheHits = rl_batch_stats_get(e_, &bs) == RL_OK ? bs.cache_hits : 0;
+    return st;
+}
+
+std::vector<uint64_t> GpuEngine::hashKeys(const KeyBatch& keys) {
+    std::vector<uint64_t> out(keys.size());
+    int st;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        st = rl_hash_keys(e_, keys.size(), keys.bytes().data(), keys.bytes().size(),
+                          keys.offsets().data(), out.data());
+    }
+    if (st == RL_E_INVALID_ARG) throw IllegalArgumentException(std::string("hashKeys: ") + rl_strerror(st));
+    if (st != RL_OK) throw StorageException(std::string("hashKeys: ") + rl_strerror(st), st);
+    return out;
 }
 
 int GpuEngine::retryAfter(size_t n, const uint64_t* key, const int32_t* permits, const int64_t* now,
@@ -453,8 +475,7 @@ std::vector<std::pair<uint64_t, int64_t>> GpuRateLimiter::topConsumers(uint32_t 
     return engine_->topConsumers(id_, now, k, minUsed);
 }
 
-void GpuRateLimiter::tryAcquireBatch(size_t n, const uint64_t* keyHash, const int32_t* permits,
-                                     const int64_t* nowNanos, bool* allowed, int64_t* remaining) {
+void GpuRateLimiter::acquireBatch(size_t n, const BatchCall& run, bool* allowed, int64_t* remaining) {
     if (n == 0) return;
     std::vector<uint16_t> lim(n, id_);
     std::vector<uint8_t> al(n);
@@ -468,8 +489,7 @@ void GpuRateLimiter::tryAcquireBatch(size_t n, const uint64_t* keyHash, const in
         flushing_ = true;
         lk.unlock();
         uint64_t hits = 0;
-        st = engine_->executeBatch(n, keyHash, permits, nowNanos, lim.data(), nullptr, al.data(),
-                                   rem.data(), &hits);
+        st = run(lim.data(), al.data(), rem.data(), &hits);
         cacheHits.increment(hits);
         lk.lock();
         flushing_ = false;
@@ -484,6 +504,20 @@ void GpuRateLimiter::tryAcquireBatch(size_t n, const uint64_t* keyHash, const in
     }
     allowedRequests.increment(ok);
     rejectedRequests.increment(n - ok);
+}
+
+void GpuRateLimiter::tryAcquireBatch(size_t n, const uint64_t* keyHash, const int32_t* permits,
+                                     const int64_t* nowNanos, bool* allowed, int64_t* remaining) {
+    acquireBatch(n, [&](const uint16_t* lim, uint8_t* al, int64_t* rem, uint64_t* hits) {
+        return engine_->executeBatch(n, keyHash, permits, nowNanos, lim, nullptr, al, rem, hits);
+    }, allowed, remaining);
+}
+
+void GpuRateLimiter::tryAcquireBatch(const KeyBatch& keys, const int32_t* permits, const int64_t* nowNanos,
+                                     bool* allowed, int64_t* remaining, uint64_t* keyHashOut) {
+    acquireBatch(keys.size(), [&](const uint16_t* lim, uint8_t* al, int64_t* rem, uint64_t* hits) {
+        return engine_->executeBatchKeys(keys, permits, nowNanos, lim, nullptr, al, rem, keyHashOut, hits);
+    }, allowed, remaining);
 }
 
 }  // namespace ratelimiter

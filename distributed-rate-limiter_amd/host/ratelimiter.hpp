@@ -21,6 +21,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <string_view>
 #include <thread>
 #include <utility>
 #include <vector>
@@ -93,8 +94,24 @@ struct Counter {
 
 // String -> 64-bit key hash (build-defined): FNV-1a over the UTF-8
 // bytes followed by the splitmix64 finaliser. Collisions between distinct strings make
-// them share state (probability ~ n^2 / 2^65).
+// them share state (probability ~ n^2 / 2^65). One definition: rl_key_hash (rl_engine.h).
 uint64_t keyHash(const std::string& key);
+
+// A batch of string keys in the layout of rl_hash_keys / rl_execute_batch_keys: the keys' UTF-8
+// bytes back to back plus size() + 1 offsets. add() throws IllegalArgumentException for a key
+// longer than RL_KEY_MAX_BYTES (the per-call tryAcquire(String) path has no such limit).
+class KeyBatch {
+  public:
+    void add(std::string_view key);
+    size_t size() const { return off_.size() - 1; }
+    const std::vector<uint8_t>& bytes() const { return bytes_; }
+    const std::vector<uint64_t>& offsets() const { return off_; }
+    void clear() { bytes_.clear(); off_.assign(1, 0); }
+
+  private:
+    std::vector<uint8_t> bytes_;
+    std::vector<uint64_t> off_ = std::vector<uint64_t>(1, 0);
+};
 
 // One GPU engine (rl_create). Thread-safe: the engine serialises batches.
 class GpuEngine {
@@ -121,6 +138,13 @@ class GpuEngine {
     int executeBatch(size_t n, const uint64_t* key, const int32_t* permits, const int64_t* now,
                      const uint16_t* limiter, const uint8_t* op, uint8_t* allowed,
                      int64_t* remaining, uint64_t* cacheHits);
+    // rl_execute_batch_keys: the same batch on string keys, hashed on the device; keyHashOut
+    // (nullable) receives keyHash of every key.
+    int executeBatchKeys(const KeyBatch& keys, const int32_t* permits, const int64_t* now,
+                         const uint16_t* limiter, const uint8_t* op, uint8_t* allowed,
+                         int64_t* remaining, uint64_t* keyHashOut, uint64_t* cacheHits);
+    // rl_hash_keys: keyHash of every key of the batch, computed on the device (read-only).
+    std::vector<uint64_t> hashKeys(const KeyBatch& keys);
     // rl_retry_after: ms until an acquire would be allowed (read-only; skip nullable).
     int retryAfter(size_t n, const uint64_t* key, const int32_t* permits, const int64_t* now,
                    const uint16_t* limiter, const uint8_t* skip, int64_t* waitMs);
@@ -235,6 +259,11 @@ class GpuRateLimiter : public RateLimiter {
     // tryAcquireBatch(keys[], permits[], nowNanos[]); remaining may be null.
     void tryAcquireBatch(size_t n, const uint64_t* keyHash, const int32_t* permits,
                          const int64_t* nowNanos, bool* allowed, int64_t* remaining);
+    // The same on string keys (keys.size() requests), hashed on the device in the batch's own
+    // submission: the decisions, counters and exceptions of the overload above on keyHash of
+    // every key; keyHashOut (nullable) receives those hashes.
+    void tryAcquireBatch(const KeyBatch& keys, const int32_t* permits, const int64_t* nowNanos,
+                         bool* allowed, int64_t* remaining, uint64_t* keyHashOut = nullptr);
 
     uint16_t limiterId() const { return id_; }
     const RateLimitConfig& config() const { return cfg_; }
@@ -256,6 +285,10 @@ class GpuRateLimiter : public RateLimiter {
     void submit(Pending& p);
     void flushLocked(std::unique_lock<std::mutex>& lk);
     void checkStatus(int st, const char* where);
+    // the body of both tryAcquireBatch overloads; run(limiter ids, allowed, remaining, cache hits)
+    // makes the engine call
+    using BatchCall = std::function<int(const uint16_t*, uint8_t*, int64_t*, uint64_t*)>;
+    void acquireBatch(size_t n, const BatchCall& run, bool* allowed, int64_t* remaining);
 
     std::shared_ptr<GpuEngine> engine_;
     Algorithm algo_;

@@ -39,6 +39,7 @@ DIGEST_CACHE = 1                           # RL_DIGEST_CACHE: also digest the re
 # RL_DIGEST_K_SW / _K_TB / _K_CACHE and RL_DIGEST_C1 / _C2 (include/rl_engine.h): the entry hash
 DIGEST_K = (0x9E3779B97F4A7C15, 0xC2B2AE3D27D4EB4F, 0x165667B19E3779F9)
 DIGEST_C1, DIGEST_C2 = 0xFF51AFD7ED558CCD, 0xC4CEB9FE1A85EC53
+KEY_MAX_BYTES = 4096                       # RL_KEY_MAX_BYTES: longest key of a string-key batch
 SNAPSHOT_MIN_CAP = 256                     # RL_SNAPSHOT_MIN_CAP: a snapshot cap that always makes progress
 SHRINK_FILL_MAX, SHRINK_LEVELS = 104, 24   # RL_SHRINK_* (rl_shrink_plan, rl_shrink_limiter)
 PUT_REJECT_ORDER, PUT_REJECT_LIMITER = 1, 2   # `rejected` bits of rl_put_keys_device's header
@@ -72,6 +73,7 @@ EXPORTS = [
     "rl_shrink_plan", "rl_shrink_limiter",
     "rl_router_execute", "rl_router_retry_after", "rl_route_partition_skip_device",
     "rl_route_fold_ops", "rl_route_unfold_ops", "rl_route_unpack_wait",
+    "rl_key_hash", "rl_hash_keys", "rl_hash_keys_device", "rl_execute_batch_keys",
 ]
 RCCL_EXPORTS = ["rl_rccl_unique_id", "rl_transport_rccl_create", "rl_transport_rccl_destroy"]
 STATE_SW_BUCKET, STATE_TB_BUCKET = 0, 1
@@ -266,6 +268,11 @@ def lib():
     L.rl_route_unpack_wait.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp]
     L.rl_router_execute.argtypes = [vp, sz] + [vp] * 8
     L.rl_router_retry_after.argtypes = [vp, sz] + [vp] * 7
+    L.rl_key_hash.argtypes = [vp, sz]
+    L.rl_key_hash.restype = ctypes.c_uint64
+    L.rl_hash_keys_device.argtypes = [vp, sz, vp, sz, vp, vp, vp, vp]
+    L.rl_hash_keys.argtypes = [vp, sz, vp, sz, vp, vp]
+    L.rl_execute_batch_keys.argtypes = [vp, sz, vp, sz] + [vp] * 9
     _lib = L
     return L
 
@@ -342,13 +349,36 @@ def digest_model(entries, cache_entries, shard_count, bucket_bits):
     return out
 
 
-def key_hash(key: str) -> int:
-    """String -> 64-bit key hash as the C++ host API computes it (host/ratelimiter.cpp
-    keyHash: FNV-1a 64 over the UTF-8 bytes, then the splitmix64 finaliser)."""
+def key_hash(key) -> int:
+    """Key bytes (or a str, taken as its UTF-8 bytes) -> the 64-bit key hash: rl_key_hash of
+    include/rl_engine.h, the one definition the C++ host API and the device kernel share.
+    Host code: no GPU is touched."""
+    b = key.encode("utf-8") if isinstance(key, str) else bytes(key)
+    return int(lib().rl_key_hash(b, len(b)))
+
+
+def key_hash_model(key) -> int:
+    """rl_key_hash restated in Python from its definition in include/rl_engine.h (FNV-1a 64
+    over the bytes, each taken as unsigned, then the splitmix64 finaliser), for tests. Not used
+    by the engine."""
+    b = key.encode("utf-8") if isinstance(key, str) else bytes(key)
     h = 0xCBF29CE484222325
-    for c in key.encode("utf-8"):
+    for c in b:
         h = ((h ^ c) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
     return int(mix64(np.uint64(h)))
+
+
+def pack_keys(keys, first_offset: int = 0):
+    """A list of keys (bytes, or str taken as UTF-8) in the layout of rl_hash_keys /
+    rl_execute_batch_keys: (blob uint8 array, off uint64 array of len(keys) + 1). The blob
+    starts with first_offset filler bytes, so off[0] = first_offset."""
+    parts = [k.encode("utf-8") if isinstance(k, str) else bytes(k) for k in keys]
+    blob = np.frombuffer(b"\xa5" * int(first_offset) + b"".join(parts), np.uint8).copy()
+    off = np.zeros(len(parts) + 1, np.uint64)
+    off[0] = first_offset
+    if parts:
+        off[1:] = np.uint64(first_offset) + np.cumsum([len(p) for p in parts], dtype=np.uint64)
+    return blob, off
 
 
 def owner_of(keys, shard_count: int):
@@ -433,6 +463,52 @@ class Engine:
         if st in (RL_E_DEVICE, RL_E_NOMEM, RL_E_TOO_LARGE):
             raise RlError(st, "rl_execute_batch")
         return allowed, remaining, tokens, st
+
+    def hash_keys(self, blob, off):
+        """rl_hash_keys on a host key batch (pack_keys): the keys' hashes, computed on the
+        device, as a uint64 array. Read-only. Raises RlError(RL_E_INVALID_ARG) for a malformed
+        offset."""
+        blob = np.ascontiguousarray(blob, np.uint8)
+        off = np.ascontiguousarray(off, np.uint64)
+        n = max(off.shape[0] - 1, 0)
+        out = np.zeros(n, np.uint64)
+        st = self._L.rl_hash_keys(self._h, n, _p(blob) if blob.shape[0] else None, blob.shape[0],
+                                  _p(off), _p(out) if n else None)
+        if st != RL_OK:
+            raise RlError(st, "rl_hash_keys")
+        return out
+
+    def hash_keys_device(self, n, key_bytes, key_bytes_len, key_off, key_hash, hdr, stream=None):
+        """rl_hash_keys_device on device buffers (torch tensors or raw pointers): key_hash[i] =
+        the hash of the bytes [key_off[i], key_off[i + 1]) of key_bytes, 0 for a malformed key;
+        hdr (2 x 8 bytes) = {malformed keys, n}. Asynchronous."""
+        st = self._L.rl_hash_keys_device(self._h, int(n), _p(key_bytes), int(key_bytes_len),
+                                         _p(key_off), _p(key_hash), _p(hdr), _p(stream))
+        if st != RL_OK:
+            raise RlError(st, "rl_hash_keys_device")
+
+    def execute_batch_keys(self, blob, off, permits, now_ns, limiter=None, ops=None, want_tokens=True,
+                           want_hashes=True):
+        """rl_execute_batch_keys: execute() on a host key batch (pack_keys), hashed on the
+        device. Returns (allowed u8, remaining i64, tokens f64|None, status, hashes u64|None)."""
+        blob = np.ascontiguousarray(blob, np.uint8)
+        off = np.ascontiguousarray(off, np.uint64)
+        permits = np.ascontiguousarray(permits, np.int32)
+        now_ns = np.ascontiguousarray(now_ns, np.int64)
+        limiter = None if limiter is None else np.ascontiguousarray(limiter, np.uint16)
+        ops = None if ops is None else np.ascontiguousarray(ops, np.uint8)
+        n = max(off.shape[0] - 1, 0)
+        allowed = np.zeros(n, np.uint8)
+        remaining = np.zeros(n, np.int64)
+        tokens = np.zeros(n, np.float64) if want_tokens else None
+        hashes = np.zeros(n, np.uint64) if want_hashes else None
+        st = self._L.rl_execute_batch_keys(self._h, n, _p(blob) if blob.shape[0] else None,
+                                           blob.shape[0], _p(off), _p(permits), _p(now_ns),
+                                           _p(limiter), _p(ops), _p(allowed), _p(remaining),
+                                           _p(tokens), _p(hashes))
+        if st in (RL_E_DEVICE, RL_E_NOMEM, RL_E_TOO_LARGE, RL_E_INVALID_ARG):
+            raise RlError(st, "rl_execute_batch_keys")
+        return allowed, remaining, tokens, st, hashes
 
     def grow_limiter(self, limiter: int, min_keys: int) -> None:
         st = self._L.rl_grow_limiter(self._h, limiter, min_keys)

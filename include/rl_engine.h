@@ -32,8 +32,9 @@
  * bindings that a Java maintainer adds on top are shown in INTEGRATION.md.
  *
  * Semantics (bit-exact with the reference):
- *  - key_hash is the caller's 64-bit hash of the String key (hashing happens on
- *    the JVM side). State is kept per (limiter id, key_hash).
+ *  - key_hash is the 64-bit hash of the String key, rl_key_hash of its UTF-8 bytes
+ *    (computed by the caller, or on the device by rl_hash_keys / rl_execute_batch_keys).
+ *    State is kept per (limiter id, key_hash).
  *  - now_ns is converted to milliseconds as floorDiv(now_ns, 1e6); the reference
  *    reads System.currentTimeMillis().
  *  - Requests of one batch are applied in array (arrival) order per key.
@@ -303,7 +304,9 @@ int  rl_sync(rl_engine* e);
  * (two-pass batches: bits of the pass-0 digit, default 12; the local grouping resolves the
  * rest), "segments" (two-pass batches: pass-0 output in that many tile segments, default 1),
  * "tile_items" (partition tile = value x 512 requests; 0 = by batch size), "sparse_max",
- * "stage_timing", "debug_regions" and the "*_per_cu" grid sizes.
+ * "stage_timing", "debug_regions" and the "*_per_cu" grid sizes; "key_stage_bytes" (the blob
+ * stage of rl_hash_keys / rl_execute_batch_keys, default 4 MiB, at least RL_KEY_MAX_BYTES) and
+ * "keys_direct" (the key-hash kernel's workgroups all take the direct-read path, default 0).
  * Every setting gives the same decisions. "fail_batches" = k makes the next k batch
  * calls fail with RL_E_DEVICE before enqueuing anything (tests of callers' error paths). */
 int  rl_tune(rl_engine* e, const char* key, int64_t value);
@@ -662,6 +665,72 @@ int  rl_limiter_digest(rl_engine* e, uint16_t limiter, int64_t now_ns, uint32_t 
                        rl_bucket_digest* total /* nullable: all buckets combined */);
 int  rl_limiter_digest_device(rl_engine* e, uint16_t limiter, int64_t now_ns, uint32_t bucket_bits,
                               uint32_t flags, rl_bucket_digest* out /* DEVICE */, void* stream);
+
+/* ---- string keys: one definition of the key hash, computed on the host or the device ------
+ * key_hash everywhere in this header is rl_key_hash of the String key's UTF-8 bytes: FNV-1a 64
+ * followed by mix64, the splitmix64 finaliser (above). All arithmetic is uint64 and wrapping;
+ * every byte c is taken as UNSIGNED (0..255):
+ *     h = 0xcbf29ce484222325;  for each byte c:  h = (h ^ c) * 0x100000001b3;
+ *     rl_key_hash = mix64(h)
+ * (0x100000001b3 = 2^40 + 0x1b3). rl_key_hash is pure host code: no GPU and no engine is
+ * needed. len == 0 is valid (`bytes` may then be NULL) and there is no length limit. This is
+ * the single definition: the C++ mirror's keyHash calls it, and a front-end either calls it
+ * too or hands its key bytes to the batch calls below, which compute the same value on the
+ * device. Fixed: part of the ABI.
+ *
+ * A key batch is key_bytes[key_bytes_len] (uint8_t, any alignment) plus key_off[n + 1]
+ * (uint64_t, 8-byte aligned): key i is the bytes [key_off[i], key_off[i + 1]), so keys are
+ * contiguous and in request order; key_off[0] need not be 0. Key i is WELL-FORMED when
+ *     key_off[i] <= key_off[i + 1],  key_off[i + 1] <= key_bytes_len  and
+ *     key_off[i + 1] - key_off[i] <= RL_KEY_MAX_BYTES;
+ * zero-length keys are legal.
+ *
+ * rl_hash_keys_device (DEVICE buffers): key_hash[i] = rl_key_hash(key i) for a well-formed
+ * key; a malformed key gets key_hash[i] = 0, none of its bytes is read, and it is counted:
+ * hdr = { malformed keys, n }, written on the stream by the call itself. Entries at and beyond
+ * n are untouched; n == 0 is valid (hdr = {0, 0}); n > 2^31 returns RL_E_TOO_LARGE. Whatever
+ * the offsets hold, the kernel reads only 16-byte-aligned granules of key_bytes that contain a
+ * byte of a well-formed key. Enqueued on `stream` (NULL = the engine's stream, joined as the
+ * other *_device calls) without a host synchronisation; returns argument or launch status
+ * only. RL_E_INVALID_ARG, before any device call and with the outputs untouched: a null engine
+ * (checked first), n > 0 with a null key_off or key_hash, a null hdr, key_bytes_len > 0 with a
+ * null key_bytes, a key_off, key_hash or hdr that is not 8-byte aligned. The call needs no
+ * engine scratch, so any number of calls may be in flight. A device-side string batch is this
+ * call followed by rl_execute_batch_device, or rl_router_step, on the same stream with
+ * key_hash as the key array: there is no fused device form and no router form.
+ *
+ * rl_hash_keys (HOST buffers): every offset is checked on the host first; any malformed key
+ * returns RL_E_INVALID_ARG with nothing written and no device call. The batch is then staged
+ * in chunks cut at key boundaries, of at most rl_opts.max_batch keys and at most the blob
+ * stage's size in bytes (default 4 MiB; rl_tune("key_stage_bytes", v), v >= RL_KEY_MAX_BYTES so
+ * that a chunk always makes progress), the device form runs per chunk, the hashes are copied
+ * back and the call synchronises. n is not bounded by max_batch. The stage memory is allocated
+ * by the first call and freed by rl_destroy. Buffers registered with rl_pin_host are DMAed
+ * directly, as by the other host-buffer calls.
+ *
+ * Both hash calls only read: no limiter state, cache word, batch statistic, and not the status
+ * rl_last_status reports, which they do not collect either.
+ *
+ * rl_execute_batch_keys (HOST buffers; the call a JNI layer uses for tryAcquire(String, int)
+ * batches): the same offset check as rl_hash_keys; n > rl_opts.max_batch returns
+ * RL_E_TOO_LARGE. The blob is staged in byte chunks and hashed on the device straight into the
+ * engine's staged key array, then exactly the batch rl_execute_batch would run is run: the
+ * outputs, the returned status (RL_E_INVALID_REQUEST and RL_E_CAPACITY included),
+ * rl_batch_stats, on-demand growth and what rl_last_status reports are those of
+ * rl_execute_batch(e, n, H, ...) with H[i] = rl_key_hash(key i). key_hash_out (nullable)
+ * receives H: the hash -> client id mapping a front-end keeps for rl_top_consumers. */
+#define RL_KEY_MAX_BYTES 4096
+uint64_t rl_key_hash(const void* bytes, size_t len);
+int  rl_hash_keys_device(rl_engine* e, size_t n, const uint8_t* key_bytes, size_t key_bytes_len,
+                         const uint64_t* key_off, uint64_t* key_hash, uint64_t* hdr /* [2] */,
+                         void* stream);
+int  rl_hash_keys(rl_engine* e, size_t n, const uint8_t* key_bytes, size_t key_bytes_len,
+                  const uint64_t* key_off, uint64_t* key_hash);
+int  rl_execute_batch_keys(rl_engine* e, size_t n, const uint8_t* key_bytes, size_t key_bytes_len,
+                           const uint64_t* key_off, const int32_t* permits, const int64_t* now_ns,
+                           const uint16_t* limiter, const uint8_t* op,
+                           uint8_t* allowed, int64_t* remaining, double* tokens_after,
+                           uint64_t* key_hash_out /* nullable */);
 
 /* ---- multi-GPU routing helpers (device buffers, engine stream) ------------
  * owner(key_hash) is the shard that holds the key's state. rl_route_partition
