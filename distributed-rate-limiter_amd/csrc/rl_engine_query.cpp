@@ -1,0 +1,483 @@
+// rl_engine_query.cpp — the read-only queries of an engine: retry-after, heavy-hitter keys, the
+// census of a limiter's table, string keys and the table digest.
+#include "rl_engine_impl.hpp"
+#include "rl_keys.hpp"
+
+using namespace rl;
+
+// ---------------------------------------------------------------- retry-after queries
+// One launch of k_retry_after on the engine stream: behind every batch submitted before it
+// (the decision stage, the hot chains' side stream and the unpermute all run on or are joined
+// on e->stream, with RL_OPT_PIPELINE too: only a batch's partition runs elsewhere). It reads
+// the limiter table as uploaded by the last growth and touches no batch scratch, statistic or
+// status word.
+static int run_retry_device(rl_engine* e, size_t n, const uint64_t* key, const int32_t* permits,
+                            const int64_t* now_ns, const uint16_t* limiter, const uint8_t* skip,
+                            int64_t* wait_ms) {
+    RetryArgs ra{};
+    ra.key = key; ra.permits = permits; ra.now_ns = now_ns; ra.limiter = limiter; ra.skip = skip;
+    ra.wait_ms = wait_ms;
+    ra.lims = e->d_lims; ra.n = (uint32_t)n; ra.n_lim = (uint32_t)e->lims.size();
+    ra.shard_bits = e->shard_bits;
+#ifdef RL_RETRY_COUNT
+    if (!e->retry_dbg) {
+        if (e->retry_dbg.reserve(3) != RL_OK) return RL_E_NOMEM;
+        HIP_OK(hipMemset(e->retry_dbg, 0, 3 * sizeof(unsigned long long)));
+    }
+    ra.dbg = e->retry_dbg;
+#endif
+    HIP_OK(launch_retry_after(ra, e->stream));
+    return RL_OK;
+}
+
+extern "C" int rl_retry_after_device(rl_engine* e, size_t n, const uint64_t* key_hash,
+                                     const int32_t* permits, const int64_t* now_ns,
+                                     const uint16_t* limiter, const uint8_t* skip,
+                                     int64_t* wait_ms, void* stream) {
+    if (!e) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (n > e->opts.max_batch) return RL_E_TOO_LARGE;
+    if (n == 0) return RL_OK;
+    if (!key_hash || !permits || !now_ns || !wait_ms) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    StreamJoin join(e->stream, (hipStream_t)stream);
+    HIP_OK(join.err);
+    const int rc = run_retry_device(e, n, key_hash, permits, now_ns, limiter, skip, wait_ms);
+    HIP_OK(join.finish());
+    return rc;
+}
+
+extern "C" int rl_retry_after(rl_engine* e, size_t n, const uint64_t* key_hash, const int32_t* permits,
+                              const int64_t* now_ns, const uint16_t* limiter, const uint8_t* skip,
+                              int64_t* wait_ms) {
+    if (!e) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (n > e->opts.max_batch) return RL_E_TOO_LARGE;
+    if (n == 0) return RL_OK;
+    if (!key_hash || !permits || !now_ns || !wait_ms) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    // as the host-buffer batch calls: the last batch's status is collected first, which applies
+    // the table growth it asked for (rl_last_status returns that same status afterwards)
+    const int st = collect_status(e);
+    if (st == RL_E_DEVICE) return st;
+    int rc = stage_requests(e, n, key_hash, permits, now_ns, limiter, skip);
+    if (rc != RL_OK) return rc;
+    hipStream_t s = e->stream;
+    rc = run_retry_device(e, n, e->s_key, e->s_permits, e->s_now, limiter ? e->s_lim : nullptr,
+                          skip ? e->s_op : nullptr, e->s_remaining);
+    if (rc != RL_OK) { (void)hipStreamSynchronize(s); return rc; }
+    HIP_OK(hipMemcpyAsync(wait_ms, e->s_remaining, n * 8, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    for (size_t i = 0; i < n; ++i)
+        if (wait_ms[i] == RL_RETRY_INVALID) return RL_E_INVALID_REQUEST;
+    return RL_OK;
+}
+
+// ---------------------------------------------------------------- heavy-hitter keys
+// rl_topk.hip on the engine stream: clear, the sketch pass and the filter pass over the keys
+// (the host form: over every staged chunk), compact + select. Nothing here touches a limiter
+// table, the batch scratch, d_stats, d_ctl or the status bookkeeping.
+static_assert(RL_TOP_KEYS_MAX == kTopkMax && RL_TOP_KEYS_MAX == kDirMax, "top keys = directory capacity");
+static_assert(RL_TOP_KEYS_CANDIDATES == kTopkCandidates, "candidate cap");
+constexpr uint64_t kTopkMaxN = 1ULL << 31;
+
+static bool topk_args_ok(rl_engine* e, size_t n, const uint64_t* key_hash, uint32_t k, uint64_t min_count) {
+    return e && (n == 0 || key_hash) && k != 0 && k <= RL_TOP_KEYS_MAX && min_count != 0 &&
+           (uint64_t)n <= kTopkMaxN;
+}
+
+static int topk_scratch(rl_engine* e, TopkScratch* sc) {
+    const int rc = e->topk.reserve(topk_scratch_bytes());
+    if (rc != RL_OK) return rc;
+    *sc = topk_scratch_at(e->topk);
+    return RL_OK;
+}
+
+extern "C" int rl_top_keys_device(rl_engine* e, size_t n, const uint64_t* key_hash, uint32_t k,
+                                  uint64_t min_count, uint64_t* top_key, uint64_t* top_count,
+                                  uint64_t* hdr, void* stream) {
+    if (!topk_args_ok(e, n, key_hash, k, min_count) || !top_key || !top_count || !hdr)
+        return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipSetDevice(e->device);
+    TopkScratch sc;
+    int rc = topk_scratch(e, &sc);
+    if (rc != RL_OK) return rc;
+    hipStream_t s = e->stream;
+    StreamJoin join(s, (hipStream_t)stream);
+    HIP_OK(join.err);
+    HIP_OK(launch_topk_clear(sc, s));
+    HIP_OK(launch_topk_pass(sc, 0, key_hash, (uint32_t)n, min_count, s));
+    HIP_OK(launch_topk_pass(sc, 1, key_hash, (uint32_t)n, min_count, s));
+    HIP_OK(launch_topk_select(sc, k, min_count, n, top_key, top_count, hdr, s));
+    HIP_OK(join.finish());
+    return RL_OK;
+}
+
+extern "C" int rl_top_keys(rl_engine* e, size_t n, const uint64_t* key_hash, uint32_t k,
+                           uint64_t min_count, uint64_t* top_key, uint64_t* top_count, size_t* n_out,
+                           uint64_t* n_heavy) {
+    if (!topk_args_ok(e, n, key_hash, k, min_count) || !top_key || !top_count || !n_out || !n_heavy)
+        return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipSetDevice(e->device);
+    TopkScratch sc;
+    int rc = topk_scratch(e, &sc);
+    if (rc != RL_OK) return rc;
+    // chunks of the staging buffers' size (at most max_batch keys, as the batch calls leave
+    // them); every chunk is uploaded once per pass
+    const size_t chunk = std::min<size_t>(std::max<size_t>(n, 1), (size_t)e->opts.max_batch);
+    rc = ensure_staging(e, chunk);
+    if (rc != RL_OK) return rc;
+    hipStream_t s = e->stream;
+    HIP_OK(launch_topk_clear(sc, s));
+    for (int pass = 0; pass < 2; ++pass)
+        for (size_t at = 0; at < n; at += chunk) {
+            const size_t m = std::min(chunk, n - at);
+            HIP_OK(hipMemcpyAsync(e->s_key, key_hash + at, m * 8, hipMemcpyHostToDevice, s));
+            HIP_OK(launch_topk_pass(sc, pass, e->s_key, (uint32_t)m, min_count, s));
+        }
+    HIP_OK(launch_topk_select(sc, k, min_count, n, sc.out_key, sc.out_cnt, sc.out_hdr, s));
+    uint64_t hdr[4] = {0, 0, 0, 0};
+    HIP_OK(hipMemcpyAsync(hdr, sc.out_hdr, sizeof(hdr), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    *n_out = 0;
+    *n_heavy = 0;
+    if (hdr[2]) return RL_E_CAPACITY;
+    if (hdr[0] > k) return RL_E_INTERNAL;
+    if (hdr[0]) {
+        HIP_OK(hipMemcpy(top_key, sc.out_key, hdr[0] * 8, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(top_count, sc.out_cnt, hdr[0] * 8, hipMemcpyDeviceToHost));
+    }
+    *n_out = (size_t)hdr[0];
+    *n_heavy = hdr[1];
+    return RL_OK;
+}
+
+// ---------------------------------------------------------------- census of a limiter's table
+// rl_usage.hip on the engine stream, behind every batch submitted before (as rl_export_state:
+// the decision stage and the unpermute run on or are joined on e->stream, with RL_OPT_PIPELINE
+// too). Both calls read the table as installed (no collect_status: a growth the last batch asked
+// for is not applied, its status stays uncollected) and touch no limiter state, batch scratch,
+// d_stats, d_ctl or status word.
+static_assert(RL_USAGE_BINS == kUsageBins, "histogram bins");
+static_assert(RL_USAGE_CANDIDATES == kUsageCandidates, "candidate cap");
+static_assert(sizeof(rl_usage) == 8 * (7 + RL_USAGE_BINS), "rl_usage layout");
+
+static int usage_scratch(rl_engine* e, UsageScratch* sc) {
+    const int rc = e->usage.reserve(usage_scratch_bytes());
+    if (rc != RL_OK) return rc;
+    *sc = usage_scratch_at(e->usage);
+    return RL_OK;
+}
+
+extern "C" int rl_limiter_usage(rl_engine* e, uint16_t limiter, int64_t now_ns, rl_usage* out) {
+    if (!e || !out) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (limiter >= e->lims.size()) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    UsageScratch sc;
+    int rc = usage_scratch(e, &sc);
+    if (rc != RL_OK) return rc;
+    const HostLimiter& h = e->lims[limiter];
+    const uint64_t n_slots = h.table_bytes / sizeof(Slot);
+    hipStream_t s = e->stream;
+    unsigned long long c[kUcWords];
+    HIP_OK(hipMemsetAsync(sc.counters, 0, 32 * sizeof(unsigned long long), s));
+    HIP_OK(launch_usage_census(sc, (const Slot*)h.table, n_slots, h.dev, floor_div_ms(now_ns), s));
+    HIP_OK(hipMemcpyAsync(c, sc.counters, sizeof(c), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    out->slots = n_slots;
+    out->used_slots = c[kUcUsedSlots];
+    out->live_keys = c[kUcLive];
+    out->redis_keys = c[kUcRedis];
+    out->exhausted_keys = c[kUcExhausted];
+    out->cache_blocked = c[kUcCacheBlocked];
+    out->used_permits = c[kUcUsedPermits];
+    for (uint32_t b = 0; b < kUsageBins; ++b) out->hist[b] = c[kUcHist + b];
+    return RL_OK;
+}
+
+// MSD radix select over C = used << 64 | ~key_hash (largest first = used descending, key_hash
+// ascending): every pass histograms the next 12-bit digit of the keys that match the prefix
+// chosen so far, the host picks the digit in which the k-th key lies, and refinement stops as
+// soon as that cut bin holds at most RL_USAGE_CANDIDATES keys (or no bit is left: one key).
+// The compaction then fetches the cut bin and the fewer than k keys above it, ordered here.
+extern "C" int rl_top_consumers(rl_engine* e, uint16_t limiter, int64_t now_ns, uint32_t k,
+                                int64_t min_used, uint64_t* key_hash, int64_t* used, size_t* n_out,
+                                uint64_t* n_match) {
+    if (!e || !key_hash || !used || !n_out || !n_match || k == 0 || k > RL_TOP_KEYS_MAX || min_used < 0)
+        return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (limiter >= e->lims.size()) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    UsageScratch sc;
+    int rc = usage_scratch(e, &sc);
+    if (rc != RL_OK) return rc;
+    const HostLimiter& h = e->lims[limiter];
+    const uint64_t n_slots = h.table_bytes / sizeof(Slot);
+    const int64_t now = floor_div_ms(now_ns);
+    hipStream_t s = e->stream;
+    uint32_t ubits = 0;                              // bit_length(max_permits): used <= max_permits
+    while (ubits < 63 && ((uint64_t)h.dev.max_permits >> ubits) != 0) ++ubits;
+    UsageSel sel{};
+    sel.min_used = min_used;
+    sel.top = ubits + 64;
+    unsigned __int128 prefix = 0;
+    std::vector<unsigned long long> hist(kUsageDigits);
+    uint64_t matched = 0, need = 0, keep = 0, cut_count = 0;
+    e->usage_passes = 0;
+    for (bool first = true;; first = false) {
+        const uint32_t width = std::min<uint32_t>(kUsageDigitBits, sel.top);
+        sel.pos = sel.top - width;
+        sel.prefix_hi = (uint64_t)(prefix >> 64);
+        sel.prefix_lo = (uint64_t)prefix;
+        HIP_OK(hipMemsetAsync(sc.hist, 0, kUsageDigits * sizeof(unsigned long long), s));
+        HIP_OK(launch_usage_digits(sc, (const Slot*)h.table, n_slots, h.dev, now, sel, s));
+        HIP_OK(hipMemcpyAsync(hist.data(), sc.hist, kUsageDigits * sizeof(unsigned long long),
+                              hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+        e->usage_passes += 1;
+        if (first) {
+            for (uint32_t b = 0; b < (1u << width); ++b) matched += hist[b];
+            if (matched == 0) {
+                *n_out = 0;
+                *n_match = 0;
+                return RL_OK;
+            }
+            keep = need = std::min<uint64_t>(k, matched);
+        }
+        // the digit that holds the need-th largest of the keys under the prefix
+        uint64_t above = 0;
+        uint32_t cut = (1u << width) - 1;
+        for (;; --cut) {
+            if (above + hist[cut] >= need) break;
+            above += hist[cut];
+            if (cut == 0) return RL_E_INTERNAL;      // (the bins sum to the previous cut bin >= need)
+        }
+        need -= above;
+        cut_count = hist[cut];
+        prefix = (prefix << width) | cut;
+        sel.top = sel.pos;
+        if (cut_count <= kUsageCandidates || sel.top == 0) break;
+    }
+    sel.prefix_hi = (uint64_t)(prefix >> 64);
+    sel.prefix_lo = (uint64_t)prefix;
+    const uint64_t expect = (keep - need) + cut_count;   // the keys above the cut bin, and the bin
+    if (expect > kUsageStore) return RL_E_INTERNAL;
+    unsigned long long got = 0;
+    HIP_OK(hipMemsetAsync(sc.counters + kUsageCandCount, 0, sizeof(unsigned long long), s));
+    HIP_OK(launch_usage_compact(sc, (const Slot*)h.table, n_slots, h.dev, now, sel, s));
+    HIP_OK(hipMemcpyAsync(&got, sc.counters + kUsageCandCount, sizeof(got), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    e->usage_passes += 1;
+    if (got != expect) return RL_E_INTERNAL;
+    std::vector<UsageCand> cand(got);
+    HIP_OK(hipMemcpy(cand.data(), sc.cand, got * sizeof(UsageCand), hipMemcpyDeviceToHost));
+    std::partial_sort(cand.begin(), cand.begin() + (long)keep, cand.end(),
+                      [](const UsageCand& x, const UsageCand& y) {
+                          return x.used != y.used ? x.used > y.used : x.key_hash < y.key_hash;
+                      });
+    for (uint64_t i = 0; i < keep; ++i) {
+        key_hash[i] = cand[i].key_hash;
+        used[i] = cand[i].used;
+    }
+    *n_out = (size_t)keep;
+    *n_match = matched;
+    return RL_OK;
+}
+
+// ---------------------------------------------------------------- string keys
+// rl_keys.hip on the engine stream. The hash calls touch no limiter table, batch scratch,
+// d_stats, d_ctl or the status bookkeeping; rl_execute_batch_keys hashes into s_key and then
+// runs the batch as rl_execute_batch does.
+static_assert(RL_KEY_MAX_BYTES == kKeyMaxBytes, "key length limit");
+constexpr uint64_t kKeysMaxN = 1ULL << 31;
+
+extern "C" uint64_t rl_key_hash(const void* bytes, size_t len) {
+    const unsigned char* b = (const unsigned char*)bytes;
+    uint64_t h = kFnvOffset;
+    for (size_t i = 0; i < len; ++i) h = (h ^ b[i]) * kFnvPrime;
+    return mix64(h);
+}
+
+static int hash_keys_enqueue(rl_engine* e, size_t n, const uint8_t* bytes, uint64_t bytes_len,
+                             const uint64_t* off, uint64_t bias, uint64_t* out, unsigned long long* hdr) {
+    HIP_OK(hipMemsetAsync(hdr, 0, 2 * sizeof(uint64_t), e->stream));
+    KeysArgs a{};
+    a.bytes = bytes; a.bytes_len = bytes_len; a.off = off; a.bias = bias; a.n = n; a.out = out;
+    a.hdr = hdr; a.direct = e->keys_direct ? 1u : 0u;
+    HIP_OK(launch_hash_keys(a, e->stream));
+    return RL_OK;
+}
+
+extern "C" int rl_hash_keys_device(rl_engine* e, size_t n, const uint8_t* key_bytes, size_t key_bytes_len,
+                                   const uint64_t* key_off, uint64_t* key_hash, uint64_t* hdr,
+                                   void* stream) {
+    if (!e) return RL_E_INVALID_ARG;
+    if ((n && (!key_off || !key_hash)) || !hdr || (key_bytes_len && !key_bytes)) return RL_E_INVALID_ARG;
+    if (((uintptr_t)key_off | (uintptr_t)key_hash | (uintptr_t)hdr) & 7u) return RL_E_INVALID_ARG;
+    if ((uint64_t)n > kKeysMaxN) return RL_E_TOO_LARGE;
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipSetDevice(e->device);
+    StreamJoin join(e->stream, (hipStream_t)stream);
+    HIP_OK(join.err);
+    const int rc = hash_keys_enqueue(e, n, key_bytes, key_bytes_len, key_off, 0, key_hash,
+                                     (unsigned long long*)hdr);
+    HIP_OK(join.finish());
+    return rc;
+}
+
+// The arguments of the two host forms; every offset is checked before any device call.
+static bool keys_host_args_ok(size_t n, const uint8_t* key_bytes, size_t key_bytes_len, const uint64_t* key_off) {
+    if (n == 0) return true;
+    if (!key_off || (key_bytes_len && !key_bytes) || ((uintptr_t)key_off & 7u)) return false;
+    return keys_first_malformed(key_off, n, key_bytes_len) == n;
+}
+
+// The blob stage and room for `keys` offsets (+ 1) and hashes.
+static int ensure_key_stage(rl_engine* e, size_t keys) {
+    if (e->ks_blob.cap != e->key_stage_bytes) e->ks_blob.free();   // (a smaller stage too)
+    int rc = e->ks_blob.reserve(e->key_stage_bytes);
+    if (rc == RL_OK) rc = e->ks_hdr.reserve(2);
+    if (rc == RL_OK) rc = e->ks_off.reserve(keys + 1);
+    if (rc == RL_OK) rc = e->ks_hash.reserve(keys);
+    return rc;
+}
+
+// One staged chunk: keys [at, at + m) of the host batch hashed into out[0, m) (device). The
+// chunk's bytes go through ks_blob; `d_off` holds the chunk's m + 1 offsets on the device.
+static int hash_keys_chunk(rl_engine* e, const uint8_t* key_bytes, const uint64_t* key_off, size_t at,
+                           size_t m, const uint64_t* d_off, uint64_t* out) {
+    const uint64_t base = key_off[at], bytes = key_off[at + m] - base;
+    if (bytes) HIP_OK(hipMemcpyAsync(e->ks_blob, key_bytes + base, bytes, hipMemcpyHostToDevice, e->stream));
+    return hash_keys_enqueue(e, m, e->ks_blob, bytes, d_off, base, out, e->ks_hdr);
+}
+
+extern "C" int rl_hash_keys(rl_engine* e, size_t n, const uint8_t* key_bytes, size_t key_bytes_len,
+                            const uint64_t* key_off, uint64_t* key_hash) {
+    if (!e) return RL_E_INVALID_ARG;
+    if ((n && !key_hash) || !keys_host_args_ok(n, key_bytes, key_bytes_len, key_off)) return RL_E_INVALID_ARG;
+    if (n == 0) return RL_OK;
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipSetDevice(e->device);
+    const size_t max_keys = (size_t)std::min<uint64_t>(e->opts.max_batch, n);
+    int rc = ensure_key_stage(e, max_keys);
+    if (rc != RL_OK) return rc;
+    hipStream_t s = e->stream;
+    for (size_t at = 0; at < n;) {
+        const size_t m = keys_chunk(key_off, n, at, max_keys, e->key_stage_bytes);
+        HIP_OK(hipMemcpyAsync(e->ks_off, key_off + at, (m + 1) * 8, hipMemcpyHostToDevice, s));
+        rc = hash_keys_chunk(e, key_bytes, key_off, at, m, e->ks_off, e->ks_hash);
+        if (rc != RL_OK) { (void)hipStreamSynchronize(s); return rc; }
+        HIP_OK(hipMemcpyAsync(key_hash + at, e->ks_hash, m * 8, hipMemcpyDeviceToHost, s));
+        at += m;
+    }
+    HIP_OK(hipStreamSynchronize(s));
+    return RL_OK;
+}
+
+extern "C" int rl_execute_batch_keys(rl_engine* e, size_t n, const uint8_t* key_bytes, size_t key_bytes_len,
+                                     const uint64_t* key_off, const int32_t* permits, const int64_t* now_ns,
+                                     const uint16_t* limiter, const uint8_t* op, uint8_t* allowed,
+                                     int64_t* remaining, double* tokens_after, uint64_t* key_hash_out) {
+    if (!e) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (n > e->opts.max_batch) return RL_E_TOO_LARGE;
+    if (n == 0) return RL_OK;
+    if (!permits || !now_ns || !allowed || !remaining) return RL_E_INVALID_ARG;
+    if (!keys_host_args_ok(n, key_bytes, key_bytes_len, key_off)) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    int rc = ensure_key_stage(e, n);
+    if (rc == RL_OK) rc = stage_requests(e, n, nullptr, permits, now_ns, limiter, op);
+    if (rc != RL_OK) return rc;
+    hipStream_t s = e->stream;
+    HIP_OK(hipMemcpyAsync(e->ks_off, key_off, (n + 1) * 8, hipMemcpyHostToDevice, s));
+    for (size_t at = 0; at < n;) {                     // byte chunks, hashed straight into s_key
+        const size_t m = keys_chunk(key_off, n, at, n, e->key_stage_bytes);
+        rc = hash_keys_chunk(e, key_bytes, key_off, at, m, e->ks_off + at, e->s_key + at);
+        if (rc != RL_OK) { (void)hipStreamSynchronize(s); return rc; }
+        at += m;
+    }
+    if (key_hash_out) HIP_OK(hipMemcpyAsync(key_hash_out, e->s_key, n * 8, hipMemcpyDeviceToHost, s));
+    return run_staged_batch(e, n, limiter != nullptr, op != nullptr, allowed, remaining, tokens_after);
+}
+
+// ---------------------------------------------------------------- table digest
+// rl_digest.hip on the engine stream, under the census' rules (above): behind every batch
+// submitted before, the table as installed, no collect_status, nothing written but `out`.
+static_assert(RL_DIGEST_K_SW == kDigestKSw && RL_DIGEST_K_TB == kDigestKTb &&
+              RL_DIGEST_K_CACHE == kDigestKCache && RL_DIGEST_C1 == kDigestC1 &&
+              RL_DIGEST_C2 == kDigestC2, "digest constants");
+static_assert(sizeof(rl_bucket_digest) == 24 && sizeof(BucketDigest) == 24, "rl_bucket_digest layout");
+
+static bool digest_args_ok(const rl_engine* e, size_t limiter, uint32_t bucket_bits, uint32_t flags) {
+    if (limiter >= e->lims.size() || (flags & ~(uint32_t)RL_DIGEST_CACHE)) return false;
+    return bucket_bits <= (uint32_t)e->lims[limiter].dev.region_bits;
+}
+
+// Zeroes out[2^bucket_bits] (device) and launches the pass, both on the engine stream; for few
+// buckets the pass writes finer ones into e->digest_fine and a fold fills `out` (rl_digest.hip).
+static int digest_enqueue(rl_engine* e, size_t li, int64_t now_ns, uint32_t bucket_bits, uint32_t flags,
+                          BucketDigest* out) {
+    const HostLimiter& h = e->lims[li];
+    DigestArgs a{};
+    a.tab = (const Slot*)h.table;
+    a.n_regions = h.table_bytes / sizeof(Slot) / kRegionSlots;
+    a.L = h.dev;
+    a.now = floor_div_ms(now_ns);
+    a.bucket_bits = bucket_bits;
+    a.with_cache = (flags & RL_DIGEST_CACHE) ? 1u : 0u;
+    a.out = out;
+    a.per_cu = e->digest_per_cu;
+    if (a.n_regions != (1ULL << h.dev.region_bits)) return RL_E_INTERNAL;   // (buckets are region ranges)
+    const uint32_t fine = std::min<uint32_t>(kDigestFineBits, (uint32_t)h.dev.region_bits);
+    if (bucket_bits < fine) {
+        const int rc = e->digest_fine.reserve((size_t)1 << kDigestFineBits);
+        if (rc != RL_OK) return rc;
+        a.bucket_bits = fine;
+        a.out = e->digest_fine;
+    }
+    HIP_OK(hipMemsetAsync(a.out, 0, sizeof(BucketDigest) << a.bucket_bits, e->stream));
+    HIP_OK(launch_digest(a, e->stream));
+    if (a.out != out) HIP_OK(launch_digest_fold(a.out, fine, out, bucket_bits, e->stream));
+    return RL_OK;
+}
+
+extern "C" int rl_limiter_digest_device(rl_engine* e, uint16_t limiter, int64_t now_ns,
+                                        uint32_t bucket_bits, uint32_t flags, rl_bucket_digest* out,
+                                        void* stream) {
+    if (!e || !out || ((uintptr_t)out & 7u)) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!digest_args_ok(e, limiter, bucket_bits, flags)) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    StreamJoin join(e->stream, (hipStream_t)stream);
+    HIP_OK(join.err);
+    int rc = digest_enqueue(e, limiter, now_ns, bucket_bits, flags, (BucketDigest*)out);
+    if (rc != RL_OK) return rc;
+    HIP_OK(join.finish());
+    return RL_OK;
+}
+
+extern "C" int rl_limiter_digest(rl_engine* e, uint16_t limiter, int64_t now_ns, uint32_t bucket_bits,
+                                 uint32_t flags, rl_bucket_digest* out, rl_bucket_digest* total) {
+    if (!e || !out) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!digest_args_ok(e, limiter, bucket_bits, flags)) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    const size_t nb = (size_t)1 << bucket_bits;
+    int rc = e->digest.reserve(nb);
+    if (rc != RL_OK) return rc;
+    rc = digest_enqueue(e, limiter, now_ns, bucket_bits, flags, e->digest);
+    if (rc != RL_OK) return rc;
+    HIP_OK(hipMemcpyAsync(out, e->digest, nb * sizeof(BucketDigest), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    if (total) {
+        rl_bucket_digest t{0, 0, 0};
+        for (size_t b = 0; b < nb; ++b) {
+            t.entries += out[b].entries; t.sum += out[b].sum; t.xr ^= out[b].xr;
+        }
+        *total = t;
+    }
+    return RL_OK;
+}

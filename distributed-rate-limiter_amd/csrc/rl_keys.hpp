@@ -1,5 +1,5 @@
 // rl_keys.hpp — the arithmetic of a string-key batch (rl_key_hash, rl_hash_keys,
-// rl_execute_batch_keys; kernel in rl_keys.hip, host side in rl_engine.cpp).
+// rl_execute_batch_keys; kernel in rl_keys.hip, host side in rl_engine_query.cpp).
 // Plain C++ with no HIP header, so tests/cpp/test_keys_plan.cpp checks it on the CPU against
 // brute force; the kernel and the engine call the same functions.
 //

@@ -316,7 +316,7 @@ struct SynthArgs {
 };
 
 // State export / import (rl_export_state / rl_import_state). StateRec has the layout of
-// rl_state_entry (include/rl_engine.h; static_assert in rl_engine.cpp).
+// rl_state_entry (include/rl_engine.h; static_assert in rl_engine_state.cpp).
 struct StateRec {
     uint64_t key_hash;
     uint16_t limiter;
@@ -339,7 +339,7 @@ struct ImportArgs {
 };
 
 // Key migration (rl_migrate.hip; rl_copy_keys / rl_drop_keys / rl_put_keys). KeyImage has the
-// layout of rl_key_image (include/rl_engine.h; static_assert in rl_engine.cpp): a slot's words
+// layout of rl_key_image (include/rl_engine.h; static_assert in rl_engine_state.cpp): a slot's words
 // and its cache word as stored.
 struct KeyImage {
     uint64_t key_hash;
@@ -594,7 +594,7 @@ hipError_t launch_usage_compact(const UsageScratch& sc, const Slot* table, uint6
 // Table digest (rl_digest.hip; rl_limiter_digest(_device), include/rl_engine.h): one read-only
 // pass over the limiter's slots that folds a hash of every entry live at `now` into out[bucket],
 // bucket = the top bucket_bits of the slot's region index. The constants are ABI
-// (RL_DIGEST_*, asserted equal in rl_engine.cpp).
+// (RL_DIGEST_*, asserted equal in rl_engine_query.cpp).
 constexpr uint64_t kDigestKSw = 0x9e3779b97f4a7c15ULL;
 constexpr uint64_t kDigestKTb = 0xc2b2ae3d27d4eb4fULL;
 constexpr uint64_t kDigestKCache = 0x165667b19e3779f9ULL;
@@ -721,7 +721,7 @@ constexpr uint32_t kStatusAccWords = 5;
 hipError_t launch_status_accum(const BatchCtl* ctl, unsigned long long flags, unsigned long long* acc,
                                hipStream_t s);
 
-// internal helpers of rl_engine.cpp for rl_router.cpp (not part of the C-ABI)
+// internal helpers of the engine units (rl_engine*.cpp) for rl_router.cpp (not part of the C-ABI)
 int route_pack_wire_mm(rl_engine* e, size_t n, const uint32_t* perm, const uint64_t* key,
                        const int32_t* permits, const int64_t* now_ns, const uint16_t* limiter,
                        uint64_t* wire_out, uint16_t* limiter_out, int64_t* hdr, uint64_t* part,

@@ -1,5 +1,5 @@
 // rl_shrink.hpp — the arithmetic of a table shrink (rl_shrink_plan / rl_shrink_limiter; kernels
-// in rl_shrink.hip, host side in rl_engine.cpp). Plain C++ with no HIP header, so
+// in rl_shrink.hip, host side in rl_engine_state.cpp). Plain C++ with no HIP header, so
 // tests/cpp/test_shrink_plan.cpp checks it on the CPU against brute force; the engine calls the
 // same functions.
 //
@@ -11,7 +11,7 @@
 //  * The halvings: j is the largest i < levels with
 //        fullest[i] <= kShrinkFillMax  and  slots_before >> i >= shrink_min_slots(min_keys).
 //    i = 0 ("leave the table alone") is always allowed. kShrinkFillMax = kGrowUsed / 2
-//    (static_assert in rl_engine.cpp): the fullest region of a shrunk table must double its
+//    (static_assert in rl_engine_state.cpp): the fullest region of a shrunk table must double its
 //    keys before a batch flags the limiter for growth again. shrink_min_slots is the load
 //    <= 0.5 rule of rl_grow_limiter with the minimum of one bin (8 regions) per limiter.
 //  * The passes: one wave merges at most 2^kShrinkPassBits = 8 source regions (64 KB) into one

@@ -1,5 +1,5 @@
 // rl_snapshot.hpp — the arithmetic of a whole-table snapshot and of an ordered put
-// (rl_snapshot_keys / rl_put_keys_device; kernels in rl_snapshot.hip, host side in rl_engine.cpp).
+// (rl_snapshot_keys / rl_put_keys_device; kernels in rl_snapshot.hip, host side in rl_engine_state.cpp).
 // Plain C++ with no HIP header, so tests/cpp/test_snapshot_plan.cpp checks it on the CPU against
 // brute force; the kernels and the engine call the same functions.
 //

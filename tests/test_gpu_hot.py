@@ -335,7 +335,7 @@ def test_hot_chain_launch_smaller_than_hot_list():
 
 @pytest.mark.parametrize("two_pass", [False, True])
 def test_hot_path_beside_cache_on_limiter(two_pass):
-    """The hot path is gated per limiter (rl_engine.cpp, k_hot_select): a Zipf-hot token
+    """The hot path is gated per limiter (rl_engine_batch.cpp, k_hot_select): a Zipf-hot token
     bucket keeps its chains — and, on two-pass tables, its pass-0 routing — while a sliding
     window with the Caffeine local cache (RateLimitConfig.java:37-38, the api limiter of
     RateLimiterConfig.java:54-55) shares the engine. The cache-on limiter has its own hot key

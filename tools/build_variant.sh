@@ -12,7 +12,7 @@ fi
 cd $src/distributed-rate-limiter_amd
 F="-O3 -std=c++17 -fPIC -ffp-contract=off --offload-arch=gfx950 -Wall -Wno-unused-result $2"
 objs=""
-for s in csrc/rl_*.hip csrc/rl_engine.cpp csrc/rl_router.cpp; do
+for s in csrc/rl_*.hip csrc/rl_engine*.cpp csrc/rl_router.cpp; do
   o=$out/$(basename ${s%.*}).o
   objs="$objs $o"
   /opt/rocm/bin/hipcc $F -x hip -c $s -o $o &
