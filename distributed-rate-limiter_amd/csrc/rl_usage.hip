@@ -24,7 +24,7 @@
 //   k_usage_compact  appends {key_hash, used} of every key with C >> top >= prefix (the cut bin
 //                    and the fewer than k keys above it) to the candidate store, one global
 //                    atomic per wave and step.
-// The host (rl_engine.cpp) drives the passes, reads the histogram between them and orders the
+// The host (rl_engine_query.cpp) drives the passes, reads the histogram between them and orders the
 // candidates.
 #include "rl_table.hpp"
 

@@ -1,4 +1,4 @@
-"""GPU parity of the hot chains' allow walk (rl_hot.hpp `walk`, k_hot_summ's per-ms tables,
+"""GPU parity of the hot chains' allow walk (rl_hot_walk.hpp `walk`, k_hot_summ's per-ms tables,
 k_hot_fill's walk verdicts): dense hot keys at their limit, whose allows the chain finds from
 the key's state and the per-ms table of first acquires instead of detailing a chunk per
 allow. Every case is compared bit-exactly with the CPU oracle (decisions, remaining, TB

@@ -1,4 +1,4 @@
-"""CPU check of the allow-walk algorithm (tools/walk_model.py, the model of rl_hot.hpp's `walk`
+"""CPU check of the allow-walk algorithm (tools/walk_model.py, the model of rl_hot_walk.hpp's `walk`
 and k_hot_fill's walk verdicts): for one key's record stream the walk (next allow from the
 state and the per-ms table of first acquires; chunk verdicts with up to 4 allows; remaining-0
 chunks; specials, bursts and fifth allows detailed) must give the sequential semantics'

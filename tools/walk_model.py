@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""CPU model of the hot chains' allow walk (rl_hot.hpp `walk`, k_hot_summ's per-ms table,
+"""CPU model of the hot chains' allow walk (rl_hot_walk.hpp `walk`, k_hot_summ's per-ms table,
 k_hot_fill's walk verdicts) for ONE key's record stream, checked against the sequential
 semantics (SlidingWindowRateLimiter.java:85-180, TokenBucketRateLimiter Lua :38-68) record by
 record. It mirrors the device loop step for step (cursor chunk with up to 4 pending allows,
@@ -154,7 +154,7 @@ def walk(recs, st0, algo, w, stats):
 
     st = dict(cc=0, po=[], ts=lo, must=False, mlast=None, K=S.copy())
 
-    def detail_at(c):                          # rl_hot.hpp walk: detail_at
+    def detail_at(c):                          # rl_hot_walk.hpp walk: detail_at
         detail(c, S)
         if mxs[c] is not None:
             st["mlast"] = mxs[c]
