@@ -232,6 +232,7 @@ struct rl_engine {
     uint64_t grows = 0;                     // region-count doublings done (rl_batch_stats)
     DevArray<unsigned long long> retry_dbg; // measurement builds (RL_RETRY_COUNT): k_retry_after's counters
     DevArray<uint8_t> topk;                 // rl_top_keys scratch (topk_scratch_bytes), on first use
+    DevArray<unsigned long long> tally;     // [kTallyRows][kTallyWords] the host form of rl_tally_batch, on first use
     DevArray<uint8_t> usage;                // rl_limiter_usage / rl_top_consumers scratch, on first use
     uint32_t usage_passes = 0;              // table passes of the last rl_top_consumers (rl_debug_fetch)
     DevArray<rl::BucketDigest> digest;      // the host form of rl_limiter_digest, largest so far

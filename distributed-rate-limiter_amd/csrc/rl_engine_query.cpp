@@ -1,7 +1,8 @@
 // rl_engine_query.cpp — the read-only queries of an engine: retry-after, heavy-hitter keys, the
-// census of a limiter's table, string keys and the table digest.
+// batch report, the census of a limiter's table, string keys and the table digest.
 #include "rl_engine_impl.hpp"
 #include "rl_keys.hpp"
+#include "rl_report.hpp"
 
 using namespace rl;
 
@@ -143,6 +144,170 @@ extern "C" int rl_top_keys(rl_engine* e, size_t n, const uint64_t* key_hash, uin
     HIP_OK(hipStreamSynchronize(s));
     *n_out = 0;
     *n_heavy = 0;
+    if (hdr[2]) return RL_E_CAPACITY;
+    if (hdr[0] > k) return RL_E_INTERNAL;
+    if (hdr[0]) {
+        HIP_OK(hipMemcpy(top_key, sc.out_key, hdr[0] * 8, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(top_count, sc.out_cnt, hdr[0] * 8, hipMemcpyDeviceToHost));
+    }
+    *n_out = (size_t)hdr[0];
+    *n_heavy = hdr[1];
+    return RL_OK;
+}
+
+// ---------------------------------------------------------------- batch report
+// rl_report.hip (the tally) and the selector passes of rl_topk.hip (top-denied) on the engine
+// stream, under the top-keys calls' rules: they read the caller's arrays of a finished batch and
+// write the caller's outputs (and their own scratch), nothing else; no collect_status.
+static_assert(RL_TALLY_ROWS == kTallyRows && RL_TALLY_UNKNOWN == kTallyUnknown &&
+              RL_TALLY_UNKNOWN == RL_MAX_LIMITERS, "tally rows");
+static_assert(sizeof(rl_limiter_tally) == kTallyWords * 8 && sizeof(rl_limiter_tally) == 96, "rl_limiter_tally layout");
+static_assert(offsetof(rl_limiter_tally, permits_denied) == kTcPermitsDenied * 8 &&
+              offsetof(rl_limiter_tally, over_max) == kTcOverMax * 8 &&
+              offsetof(rl_limiter_tally, resets) == kTcResets * 8, "rl_limiter_tally field order");
+static_assert(RL_REMAINING_UNKNOWN == kReportRemUnknown && RL_REMAINING_ERROR == kReportRemError &&
+              RL_OP_ACQUIRE == 0 && RL_OP_PEEK == 1 && RL_OP_RESET == 2, "report constants");
+constexpr uint64_t kTallyMaxN = 1ULL << 31;
+constexpr size_t kTallyBytes = (size_t)kTallyRows * sizeof(rl_limiter_tally);
+
+static bool tally_args_ok(size_t n, const int32_t* permits, const uint8_t* allowed, const int64_t* remaining,
+                          const rl_limiter_tally* out, uint32_t flags) {
+    return (n == 0 || (permits && allowed && remaining)) && out && !(flags & ~(uint32_t)RL_TALLY_ACCUMULATE);
+}
+
+static int tally_enqueue(rl_engine* e, size_t n, const int32_t* permits, const uint16_t* limiter,
+                         const uint8_t* op, const uint8_t* allowed, const int64_t* remaining,
+                         unsigned long long* out) {
+    TallyArgs a{};
+    a.permits = permits; a.limiter = limiter; a.op = op; a.allowed = allowed; a.remaining = remaining;
+    a.out = out; a.n = (uint32_t)n; a.n_lim = (uint32_t)e->lims.size();
+    HIP_OK(launch_tally(a, e->stream));
+    return RL_OK;
+}
+
+extern "C" int rl_tally_batch_device(rl_engine* e, size_t n, const int32_t* permits, const uint16_t* limiter,
+                                     const uint8_t* op, const uint8_t* allowed, const int64_t* remaining,
+                                     rl_limiter_tally* out, uint32_t flags, void* stream) {
+    if (!e) return RL_E_INVALID_ARG;
+    if (!tally_args_ok(n, permits, allowed, remaining, out, flags) || ((uintptr_t)out & 7u))
+        return RL_E_INVALID_ARG;
+    if ((uint64_t)n > kTallyMaxN) return RL_E_TOO_LARGE;
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipSetDevice(e->device);
+    StreamJoin join(e->stream, (hipStream_t)stream);
+    HIP_OK(join.err);
+    if (!(flags & RL_TALLY_ACCUMULATE)) HIP_OK(hipMemsetAsync(out, 0, kTallyBytes, e->stream));
+    const int rc = tally_enqueue(e, n, permits, limiter, op, allowed, remaining, (unsigned long long*)out);
+    if (rc != RL_OK) return rc;
+    HIP_OK(join.finish());
+    return RL_OK;
+}
+
+extern "C" int rl_tally_batch(rl_engine* e, size_t n, const int32_t* permits, const uint16_t* limiter,
+                              const uint8_t* op, const uint8_t* allowed, const int64_t* remaining,
+                              rl_limiter_tally* out, uint32_t flags) {
+    if (!e) return RL_E_INVALID_ARG;
+    if (!tally_args_ok(n, permits, allowed, remaining, out, flags)) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipSetDevice(e->device);
+    // pieces of the staging buffers' size, as rl_top_keys; every piece adds to e->tally
+    const size_t chunk = std::min<size_t>(std::max<size_t>(n, 1), (size_t)e->opts.max_batch);
+    int rc = ensure_staging(e, chunk);
+    if (rc == RL_OK) rc = e->tally.reserve((size_t)kTallyRows * kTallyWords);
+    if (rc != RL_OK) return rc;
+    hipStream_t s = e->stream;
+    if (flags & RL_TALLY_ACCUMULATE) HIP_OK(hipMemcpyAsync(e->tally, out, kTallyBytes, hipMemcpyHostToDevice, s));
+    else HIP_OK(hipMemsetAsync(e->tally, 0, kTallyBytes, s));
+    for (size_t at = 0; at < n; at += chunk) {
+        const size_t m = std::min(chunk, n - at);
+        HIP_OK(hipMemcpyAsync(e->s_permits, permits + at, m * 4, hipMemcpyHostToDevice, s));
+        if (limiter) HIP_OK(hipMemcpyAsync(e->s_lim, limiter + at, m * 2, hipMemcpyHostToDevice, s));
+        if (op) HIP_OK(hipMemcpyAsync(e->s_op, op + at, m, hipMemcpyHostToDevice, s));
+        HIP_OK(hipMemcpyAsync(e->s_allowed, allowed + at, m, hipMemcpyHostToDevice, s));
+        HIP_OK(hipMemcpyAsync(e->s_remaining, remaining + at, m * 8, hipMemcpyHostToDevice, s));
+        rc = tally_enqueue(e, m, e->s_permits, limiter ? e->s_lim.p : nullptr, op ? e->s_op.p : nullptr,
+                           e->s_allowed, e->s_remaining, e->tally);
+        if (rc != RL_OK) { (void)hipStreamSynchronize(s); return rc; }
+    }
+    HIP_OK(hipMemcpyAsync(out, e->tally, kTallyBytes, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    return RL_OK;
+}
+
+// The selector over staged or caller arrays for limiter `sel` (checked by the caller).
+static TopkSel topk_sel(const rl_engine* e, const int32_t* permits, const uint16_t* limiter, const uint8_t* op,
+                        const uint8_t* allowed, const int64_t* remaining, uint16_t sel) {
+    TopkSel s{};
+    s.permits = permits; s.limiter = limiter; s.op = op; s.allowed = allowed; s.remaining = remaining;
+    s.n_lim = (uint32_t)e->lims.size(); s.sel = sel;
+    return s;
+}
+
+extern "C" int rl_top_denied_device(rl_engine* e, size_t n, const uint64_t* key_hash, const int32_t* permits,
+                                    const uint16_t* limiter, const uint8_t* op, const uint8_t* allowed,
+                                    const int64_t* remaining, uint16_t sel_limiter, uint32_t k,
+                                    uint64_t min_count, uint64_t* top_key, uint64_t* top_count,
+                                    uint64_t* hdr, void* stream) {
+    if (!topk_args_ok(e, n, key_hash, k, min_count) || !top_key || !top_count || !hdr ||
+        (n && (!permits || !allowed || !remaining)))
+        return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (sel_limiter >= e->lims.size()) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    TopkScratch sc;
+    int rc = topk_scratch(e, &sc);
+    if (rc != RL_OK) return rc;
+    const TopkSel sel = topk_sel(e, permits, limiter, op, allowed, remaining, sel_limiter);
+    hipStream_t s = e->stream;
+    StreamJoin join(s, (hipStream_t)stream);
+    HIP_OK(join.err);
+    HIP_OK(launch_topk_clear(sc, s));
+    HIP_OK(launch_topk_pass_sel(sc, 0, key_hash, sel, (uint32_t)n, min_count, s));
+    HIP_OK(launch_topk_pass_sel(sc, 1, key_hash, sel, (uint32_t)n, min_count, s));
+    HIP_OK(launch_topk_select(sc, k, min_count, n, top_key, top_count, hdr, s, true));
+    HIP_OK(join.finish());
+    return RL_OK;
+}
+
+extern "C" int rl_top_denied(rl_engine* e, size_t n, const uint64_t* key_hash, const int32_t* permits,
+                             const uint16_t* limiter, const uint8_t* op, const uint8_t* allowed,
+                             const int64_t* remaining, uint16_t sel_limiter, uint32_t k, uint64_t min_count,
+                             uint64_t* top_key, uint64_t* top_count, size_t* n_out, uint64_t* n_heavy,
+                             uint64_t* n_denied) {
+    if (!topk_args_ok(e, n, key_hash, k, min_count) || !top_key || !top_count || !n_out || !n_heavy ||
+        (n && (!permits || !allowed || !remaining)))
+        return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (sel_limiter >= e->lims.size()) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    TopkScratch sc;
+    int rc = topk_scratch(e, &sc);
+    if (rc != RL_OK) return rc;
+    const size_t chunk = std::min<size_t>(std::max<size_t>(n, 1), (size_t)e->opts.max_batch);
+    rc = ensure_staging(e, chunk);
+    if (rc != RL_OK) return rc;
+    const TopkSel sel = topk_sel(e, e->s_permits, limiter ? e->s_lim.p : nullptr, op ? e->s_op.p : nullptr,
+                                 e->s_allowed, e->s_remaining, sel_limiter);
+    hipStream_t s = e->stream;
+    HIP_OK(launch_topk_clear(sc, s));
+    for (int pass = 0; pass < 2; ++pass)
+        for (size_t at = 0; at < n; at += chunk) {
+            const size_t m = std::min(chunk, n - at);
+            HIP_OK(hipMemcpyAsync(e->s_key, key_hash + at, m * 8, hipMemcpyHostToDevice, s));
+            HIP_OK(hipMemcpyAsync(e->s_permits, permits + at, m * 4, hipMemcpyHostToDevice, s));
+            if (limiter) HIP_OK(hipMemcpyAsync(e->s_lim, limiter + at, m * 2, hipMemcpyHostToDevice, s));
+            if (op) HIP_OK(hipMemcpyAsync(e->s_op, op + at, m, hipMemcpyHostToDevice, s));
+            HIP_OK(hipMemcpyAsync(e->s_allowed, allowed + at, m, hipMemcpyHostToDevice, s));
+            HIP_OK(hipMemcpyAsync(e->s_remaining, remaining + at, m * 8, hipMemcpyHostToDevice, s));
+            HIP_OK(launch_topk_pass_sel(sc, pass, e->s_key, sel, (uint32_t)m, min_count, s));
+        }
+    HIP_OK(launch_topk_select(sc, k, min_count, n, sc.out_key, sc.out_cnt, sc.out_hdr, s, true));
+    uint64_t hdr[4] = {0, 0, 0, 0};
+    HIP_OK(hipMemcpyAsync(hdr, sc.out_hdr, sizeof(hdr), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    *n_out = 0;
+    *n_heavy = 0;
+    if (n_denied) *n_denied = hdr[3];
     if (hdr[2]) return RL_E_CAPACITY;
     if (hdr[0] > k) return RL_E_INTERNAL;
     if (hdr[0]) {

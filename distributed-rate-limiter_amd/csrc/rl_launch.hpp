@@ -533,7 +533,19 @@ struct TopkCtl {
                                    // kTopkCandidates qualify
     uint32_t special;              // occurrences of the key ~0 (the tables' empty mark)
     uint32_t heavy;                // keys that qualify = n_heavy (the list holds them)
-    uint32_t pad[12];
+    uint32_t selected;             // keys the selector let through (rl_top_denied: |S|), by pass 0
+    uint32_t pad[11];
+};
+// The selector of rl_top_denied: key i takes part iff its request's row is `sel` and its class
+// is DENIED (rl_report.hpp), read from the batch's arrays beside the key.
+struct TopkSel {
+    const int32_t* permits;
+    const uint16_t* limiter;       // nullable: limiter 0
+    const uint8_t* op;             // nullable: RL_OP_ACQUIRE
+    const uint8_t* allowed;
+    const int64_t* remaining;
+    uint32_t n_lim;
+    uint32_t sel;                  // < n_lim
 };
 struct TopkScratch {
     TopkCtl* ctl;
@@ -552,9 +564,28 @@ hipError_t launch_topk_clear(const TopkScratch& sc, hipStream_t s);
 // pass 0: sketch; pass 1: filter and exact count (after every chunk's pass 0)
 hipError_t launch_topk_pass(const TopkScratch& sc, int pass, const uint64_t* key, uint32_t n,
                             uint64_t min_count, hipStream_t s);
+// The same passes over the selected keys only; pass 0 adds their number to ctl.selected.
+hipError_t launch_topk_pass_sel(const TopkScratch& sc, int pass, const uint64_t* key, const TopkSel& sel,
+                                uint32_t n, uint64_t min_count, hipStream_t s);
 // compact + select: writes top_key / top_count [0, n_out) and hdr = {n_out, n_heavy, overflow, n}
+// (count_selected: hdr[3] = ctl.selected instead of n)
 hipError_t launch_topk_select(const TopkScratch& sc, uint32_t k, uint64_t min_count, uint64_t n,
-                              uint64_t* top_key, uint64_t* top_count, uint64_t* hdr, hipStream_t s);
+                              uint64_t* top_key, uint64_t* top_count, uint64_t* hdr, hipStream_t s,
+                              bool count_selected = false);
+// Per-limiter counts of a finished batch (rl_report.hip; rl_tally_batch(_device),
+// include/rl_engine.h): adds every request's row / class counters (rl_report.hpp) to
+// out[kTallyRows][kTallyWords]; the caller zeroes `out` on the stream first unless it accumulates.
+struct TallyArgs {
+    const int32_t* permits;
+    const uint16_t* limiter;       // nullable: limiter 0
+    const uint8_t* op;             // nullable: RL_OP_ACQUIRE
+    const uint8_t* allowed;
+    const int64_t* remaining;
+    unsigned long long* out;       // 8-byte aligned
+    uint32_t n;                    // <= 2^31
+    uint32_t n_lim;
+};
+hipError_t launch_tally(const TallyArgs& a, hipStream_t s);
 // Census of one limiter's table (rl_usage.hip): every kernel is one read-only pass over the
 // limiter's slots (and cache words) that evaluates each slot with the peek code at `now`.
 // One scratch of fixed size (usage_scratch_bytes) holds the counters, the digit histogram of

@@ -19,6 +19,8 @@
 //                   over the keys (8 x 8 bits) finds the last element kept; the at most 4096
 //                   kept ones are sorted in LDS (bitonic) and written with the header.
 // The host form runs the passes once per staged chunk; the device form once over the array.
+// rl_top_denied runs the same five launches with the passes' selector instantiation
+// (k_topk_pass<PASS, true>): only the keys of the requests denied under one limiter enter.
 //
 // Both passes aggregate equal keys inside the workgroup before they touch global memory: a
 // tile of 2048 keys goes into an LDS hash table {key, count} with LDS atomics, and the table is
@@ -34,6 +36,7 @@
 // ctl.special in global memory) and joins the candidates in k_topk_compact. Every 64-bit value
 // is therefore a legal key. Counts are u32 (n <= 2^31); every comparison is unsigned.
 #include "rl_kcommon.hpp"
+#include "rl_report.hpp"
 
 namespace rl {
 
@@ -121,9 +124,12 @@ __device__ inline void flush_one(const TopkScratch& sc, uint64_t key, uint32_t c
     else flush_table(sc, key, c, min_count);
 }
 
-template <int PASS>
+// SEL: only the keys of the requests the selector takes (rl_top_denied) enter the LDS table; a
+// lane whose request is not selected contributes nothing. Pass 0 counts the selected ones into
+// ctl.selected, one add per workgroup. Without SEL the selector is not looked at.
+template <int PASS, bool SEL>
 __global__ __launch_bounds__(kPassThreads) void k_topk_pass(TopkScratch sc, const uint64_t* __restrict__ key,
-                                                            uint32_t n, uint64_t min_count) {
+                                                            TopkSel sel, uint32_t n, uint64_t min_count) {
     __shared__ unsigned long long l_key[kLdsSlots];
     __shared__ uint32_t l_cnt[kLdsSlots];
     __shared__ uint32_t l_special;                 // occurrences of the key ~0
@@ -131,7 +137,8 @@ __global__ __launch_bounds__(kPassThreads) void k_topk_pass(TopkScratch sc, cons
                                                    // summed at [(r + 1) % 3], zeroed at [(r + 2) % 3]
     const uint32_t tid = threadIdx.x;
     for (uint32_t i = tid; i < kLdsSlots; i += kPassThreads) { l_key[i] = kEmptyKey; l_cnt[i] = 0; }
-    if (tid == 0) { l_special = 0; l_kept[0] = 0; l_kept[1] = 0; l_kept[2] = 0; }
+    __shared__ uint32_t l_selected;                // SEL, pass 0: selected requests of this workgroup
+    if (tid == 0) { l_special = 0; l_kept[0] = 0; l_kept[1] = 0; l_kept[2] = 0; l_selected = 0; }
     __syncthreads();
 
     const uint32_t tiles = (n + kTileKeys - 1) / kTileKeys;          // n <= 2^31: no wrap
@@ -146,6 +153,21 @@ __global__ __launch_bounds__(kPassThreads) void k_topk_pass(TopkScratch sc, cons
             const uint32_t i = base + (uint32_t)j * kPassThreads + tid;
             on[j] = i < n;
             k[j] = on[j] ? key[i] : 0;
+            if constexpr (SEL) {
+                if (on[j]) {
+                    const uint32_t lim = sel.limiter ? sel.limiter[i] : 0u;
+                    const uint32_t op = sel.op ? sel.op[i] : 0u;
+                    on[j] = report_row(lim, sel.n_lim) == sel.sel &&
+                            report_class(lim, sel.n_lim, op, sel.permits[i], sel.allowed[i],
+                                         sel.remaining[i]) == kRcDenied;
+                }
+            }
+        }
+        if constexpr (SEL && PASS == 0) {
+            uint32_t mine = 0;
+#pragma unroll
+            for (int j = 0; j < kPerThread; ++j) mine += on[j] ? 1u : 0u;
+            if (mine) atomicAdd(&l_selected, mine);
         }
 #pragma unroll
         for (int j = 0; j < kPerThread; ++j) {
@@ -187,6 +209,9 @@ __global__ __launch_bounds__(kPassThreads) void k_topk_pass(TopkScratch sc, cons
         }
         if (kept) atomicAdd(&l_kept[(round + 1) % 3], kept);
         __syncthreads();
+    }
+    if constexpr (SEL && PASS == 0) {                                // (behind the last tile's barrier)
+        if (tid == 0 && l_selected) atomicAdd(&sc.ctl->selected, l_selected);
     }
 }
 
@@ -264,10 +289,11 @@ __device__ inline uint32_t pick_digit(const uint32_t* hist, uint32_t* grp, bool 
     return g * 16 + (descending ? 0u : 15u);                         // unreachable
 }
 
-__global__ __launch_bounds__(kSelThreads) void k_topk_select(TopkScratch sc, uint32_t k, uint64_t n,
+__global__ __launch_bounds__(kSelThreads) void k_topk_select(TopkScratch sc, uint32_t k, uint64_t n_in,
                                                              uint64_t* __restrict__ top_key,
                                                              uint64_t* __restrict__ top_count,
-                                                             uint64_t* __restrict__ hdr) {
+                                                             uint64_t* __restrict__ hdr,
+                                                             uint32_t count_selected) {
     __shared__ uint64_t s_key[kTopkMax];
     __shared__ uint32_t s_cnt[kTopkMax];
     __shared__ uint32_t s_hist[256];
@@ -275,6 +301,7 @@ __global__ __launch_bounds__(kSelThreads) void k_topk_select(TopkScratch sc, uin
     __shared__ uint32_t s_fill;
     const uint32_t tid = threadIdx.x;
     const TopkCtl* ctl = sc.ctl;
+    const uint64_t n = count_selected ? (uint64_t)ctl->selected : n_in;   // hdr[3]
     if (ctl->overflow) {
         if (tid == 0) { hdr[0] = 0; hdr[1] = 0; hdr[2] = 1; hdr[3] = n; }
         return;
@@ -385,17 +412,30 @@ hipError_t launch_topk_pass(const TopkScratch& sc, int pass, const uint64_t* key
     if (n == 0) return hipSuccess;
     const uint32_t tiles = (n + kTileKeys - 1) / kTileKeys;
     const uint32_t grid = tiles < (uint32_t)kPassGridMax ? tiles : (uint32_t)kPassGridMax;
-    if (pass == 0) hipLaunchKernelGGL(k_topk_pass<0>, dim3(grid), dim3(kPassThreads), 0, s, sc, key, n, min_count);
-    else hipLaunchKernelGGL(k_topk_pass<1>, dim3(grid), dim3(kPassThreads), 0, s, sc, key, n, min_count);
+    const TopkSel none{};
+    if (pass == 0) hipLaunchKernelGGL((k_topk_pass<0, false>), dim3(grid), dim3(kPassThreads), 0, s, sc, key, none, n, min_count);
+    else hipLaunchKernelGGL((k_topk_pass<1, false>), dim3(grid), dim3(kPassThreads), 0, s, sc, key, none, n, min_count);
+    return hipGetLastError();
+}
+
+hipError_t launch_topk_pass_sel(const TopkScratch& sc, int pass, const uint64_t* key, const TopkSel& sel,
+                                uint32_t n, uint64_t min_count, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const uint32_t tiles = (n + kTileKeys - 1) / kTileKeys;
+    const uint32_t grid = tiles < (uint32_t)kPassGridMax ? tiles : (uint32_t)kPassGridMax;
+    if (pass == 0) hipLaunchKernelGGL((k_topk_pass<0, true>), dim3(grid), dim3(kPassThreads), 0, s, sc, key, sel, n, min_count);
+    else hipLaunchKernelGGL((k_topk_pass<1, true>), dim3(grid), dim3(kPassThreads), 0, s, sc, key, sel, n, min_count);
     return hipGetLastError();
 }
 
 hipError_t launch_topk_select(const TopkScratch& sc, uint32_t k, uint64_t min_count, uint64_t n,
-                              uint64_t* top_key, uint64_t* top_count, uint64_t* hdr, hipStream_t s) {
+                              uint64_t* top_key, uint64_t* top_count, uint64_t* hdr, hipStream_t s,
+                              bool count_selected) {
     hipLaunchKernelGGL(k_topk_compact, dim3(kTopkTableSlots / kCompactChunk), dim3(256), 0, s, sc, min_count);
     hipError_t rc = hipGetLastError();
     if (rc != hipSuccess) return rc;
-    hipLaunchKernelGGL(k_topk_select, dim3(1), dim3(kSelThreads), 0, s, sc, k, n, top_key, top_count, hdr);
+    hipLaunchKernelGGL(k_topk_select, dim3(1), dim3(kSelThreads), 0, s, sc, k, n, top_key, top_count, hdr,
+                       count_selected ? 1u : 0u);
     return hipGetLastError();
 }
 

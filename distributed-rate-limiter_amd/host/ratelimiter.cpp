@@ -113,6 +113,48 @@ std::vector<std::pair<uint64_t, uint64_t>> GpuEngine::topKeys(const uint64_t* ha
     return out;
 }
 
+std::vector<std::pair<uint16_t, rl_limiter_tally>> GpuEngine::tallyBatch(size_t n, const int32_t* permits,
+                                                                         const uint16_t* limiter,
+                                                                         const uint8_t* op, const uint8_t* allowed,
+                                                                         const int64_t* remaining) {
+    std::vector<rl_limiter_tally> rows(RL_TALLY_ROWS);
+    int st;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        st = rl_tally_batch(e_, n, permits, limiter, op, allowed, remaining, rows.data(), 0);
+    }
+    if (st == RL_E_INVALID_ARG) throw IllegalArgumentException(std::string("tallyBatch: ") + rl_strerror(st));
+    if (st != RL_OK) throw StorageException(std::string("tallyBatch: ") + rl_strerror(st), st);
+    std::vector<std::pair<uint16_t, rl_limiter_tally>> out;
+    for (size_t r = 0; r < rows.size(); ++r)
+        if (rows[r].requests) out.emplace_back((uint16_t)r, rows[r]);
+    return out;
+}
+
+std::vector<std::pair<uint64_t, uint64_t>> GpuEngine::topDenied(size_t n, const uint64_t* hashes,
+                                                                const int32_t* permits, const uint16_t* limiterIds,
+                                                                const uint8_t* op, const uint8_t* allowed,
+                                                                const int64_t* remaining, uint16_t limiter,
+                                                                uint32_t k, uint64_t minCount, uint64_t* nDenied) {
+    if (k == 0 || k > RL_TOP_KEYS_MAX || minCount == 0 || (n && !hashes))
+        throw IllegalArgumentException("topDenied: k in [1, RL_TOP_KEYS_MAX], minCount >= 1");
+    std::vector<uint64_t> key(k), cnt(k);
+    size_t nOut = 0;
+    uint64_t nHeavy = 0, denied = 0;
+    int st;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        st = rl_top_denied(e_, n, hashes, permits, limiterIds, op, allowed, remaining, limiter, k, minCount,
+                           key.data(), cnt.data(), &nOut, &nHeavy, &denied);
+    }
+    if (st == RL_E_INVALID_ARG) throw IllegalArgumentException(std::string("topDenied: ") + rl_strerror(st));
+    if (st != RL_OK) throw StorageException(std::string("topDenied: ") + rl_strerror(st), st);
+    if (nDenied) *nDenied = denied;
+    std::vector<std::pair<uint64_t, uint64_t>> out(nOut);
+    for (size_t i = 0; i < nOut; ++i) out[i] = {key[i], cnt[i]};
+    return out;
+}
+
 rl_usage GpuEngine::usage(uint16_t limiter, int64_t nowNanos) {
     rl_usage u{};
     int st;

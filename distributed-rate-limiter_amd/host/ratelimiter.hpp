@@ -154,6 +154,26 @@ class GpuEngine {
     // (RL_E_CAPACITY), IllegalArgumentException for k == 0, k > RL_TOP_KEYS_MAX, minCount == 0.
     std::vector<std::pair<uint64_t, uint64_t>> topKeys(const uint64_t* hashes, size_t n, uint32_t k,
                                                        uint64_t minCount);
+    // rl_tally_batch: the per-limiter counts of a finished batch (its submitted permits / limiter /
+    // op and its answered allowed / remaining; limiter and op nullable), as (row, tally) pairs of
+    // the rows with requests > 0 in ascending row order; row RL_TALLY_UNKNOWN collects the
+    // requests under ids this engine does not know. A row's tally.allowed / tally.denied are the
+    // reference's meters for that limiter and batch: ratelimiter.requests.allowed / .rejected
+    // for a sliding window (SlidingWindowRateLimiter.java:67-77), ratelimiter.tokenbucket.allowed
+    // / .rejected for a token bucket (TokenBucketRateLimiter.java:87-93; over_max, its
+    // permits > maxPermits rejections of :114, is part of denied). Read-only.
+    std::vector<std::pair<uint16_t, rl_limiter_tally>> tallyBatch(size_t n, const int32_t* permits,
+                                                                  const uint16_t* limiter, const uint8_t* op,
+                                                                  const uint8_t* allowed,
+                                                                  const int64_t* remaining);
+    // rl_top_denied: the (key hash, denials) pairs of the at most k keys most often denied under
+    // `limiter` in a finished batch, among those denied at least minCount times; order and
+    // exceptions as topKeys. nDenied (nullable) = the batch's denials under that limiter.
+    std::vector<std::pair<uint64_t, uint64_t>> topDenied(size_t n, const uint64_t* hashes, const int32_t* permits,
+                                                         const uint16_t* limiterIds, const uint8_t* op,
+                                                         const uint8_t* allowed, const int64_t* remaining,
+                                                         uint16_t limiter, uint32_t k, uint64_t minCount,
+                                                         uint64_t* nDenied = nullptr);
     // rl_limiter_usage: census of a limiter's table at nowNanos (read-only).
     rl_usage usage(uint16_t limiter, int64_t nowNanos);
     // rl_top_consumers: the (key hash, used permits) pairs of the at most k live keys of the

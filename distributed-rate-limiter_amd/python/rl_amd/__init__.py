@@ -33,6 +33,7 @@ REM_UNKNOWN, REM_INVALID, REM_ERROR = -1, -2, -3
 RETRY_NEVER, RETRY_INVALID = -1, -2   # RL_RETRY_* (rl_retry_after)
 RETRY_ERROR = -3                      # RL_RETRY_ERROR (rl_router_retry_after: the owner's call failed)
 TOP_KEYS_MAX, TOP_KEYS_CANDIDATES = 4096, 65536   # RL_TOP_KEYS_* (rl_top_keys)
+TALLY_ROWS, TALLY_UNKNOWN, TALLY_ACCUMULATE = 256, 255, 1   # RL_TALLY_* (rl_tally_batch)
 USAGE_BINS, USAGE_CANDIDATES = 16, 65536   # RL_USAGE_* (rl_limiter_usage, rl_top_consumers)
 MOVE_KEYS_MAX = 8192                       # RL_MOVE_KEYS_MAX: keys per rl_copy_keys / rl_drop_keys
 DIGEST_CACHE = 1                           # RL_DIGEST_CACHE: also digest the rejecting local-cache entries
@@ -74,6 +75,7 @@ EXPORTS = [
     "rl_router_execute", "rl_router_retry_after", "rl_route_partition_skip_device",
     "rl_route_fold_ops", "rl_route_unfold_ops", "rl_route_unpack_wait",
     "rl_key_hash", "rl_hash_keys", "rl_hash_keys_device", "rl_execute_batch_keys",
+    "rl_tally_batch", "rl_tally_batch_device", "rl_top_denied", "rl_top_denied_device",
 ]
 RCCL_EXPORTS = ["rl_rccl_unique_id", "rl_transport_rccl_create", "rl_transport_rccl_destroy"]
 STATE_SW_BUCKET, STATE_TB_BUCKET = 0, 1
@@ -120,6 +122,18 @@ class Usage(ctypes.Structure):
                                                  "exhausted_keys", "cache_blocked",
                                                  "used_permits")] + \
                [("hist", ctypes.c_uint64 * USAGE_BINS)]
+
+
+class LimiterTally(ctypes.Structure):
+    """rl_limiter_tally (include/rl_engine.h): one limiter's counts of a finished batch."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("requests", "invalid", "errors", "allowed", "denied",
+                                                 "over_max", "peeks", "resets", "permits_allowed",
+                                                 "permits_denied")] + \
+               [("reserved", ctypes.c_uint64 * 2)]
+
+
+TALLY_DTYPE = np.dtype([(n, "<u8") for n, _ in LimiterTally._fields_[:10]] + [("reserved", "<u8", (2,))])
+assert TALLY_DTYPE.itemsize == ctypes.sizeof(LimiterTally) == 96
 
 
 class BucketDigest(ctypes.Structure):
@@ -273,6 +287,12 @@ def lib():
     L.rl_hash_keys_device.argtypes = [vp, sz, vp, sz, vp, vp, vp, vp]
     L.rl_hash_keys.argtypes = [vp, sz, vp, sz, vp, vp]
     L.rl_execute_batch_keys.argtypes = [vp, sz, vp, sz] + [vp] * 9
+    L.rl_tally_batch.argtypes = [vp, sz] + [vp] * 6 + [u32]
+    L.rl_tally_batch_device.argtypes = [vp, sz] + [vp] * 6 + [u32, vp]
+    L.rl_top_denied.argtypes = [vp, sz] + [vp] * 6 + [u16, u32, ctypes.c_uint64, vp, vp, ctypes.POINTER(sz),
+                                                      ctypes.POINTER(ctypes.c_uint64),
+                                                      ctypes.POINTER(ctypes.c_uint64)]
+    L.rl_top_denied_device.argtypes = [vp, sz] + [vp] * 6 + [u16, u32, ctypes.c_uint64, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -621,6 +641,85 @@ class Engine:
         if overflow:
             raise RlError(RL_E_CAPACITY, "rl_top_keys_device")
         return top[:n_out].view(torch.uint64), cnt[:n_out].view(torch.uint64), n_heavy
+
+    def tally_batch(self, permits, limiter, ops, allowed, remaining, out=None):
+        """Per-limiter counts of a finished host batch (rl_tally_batch): a TALLY_DTYPE array of
+        TALLY_ROWS rows, row = limiter id, TALLY_UNKNOWN for ids the engine does not know.
+        `limiter` and `ops` may be None. With `out` (such an array) the counts are added to it
+        (RL_TALLY_ACCUMULATE) and it is returned. Read-only."""
+        permits = np.ascontiguousarray(permits, np.int32)
+        limiter = None if limiter is None else np.ascontiguousarray(limiter, np.uint16)
+        ops = None if ops is None else np.ascontiguousarray(ops, np.uint8)
+        allowed = np.ascontiguousarray(allowed, np.uint8)
+        remaining = np.ascontiguousarray(remaining, np.int64)
+        flags = 0 if out is None else TALLY_ACCUMULATE
+        if out is None:
+            out = np.zeros(TALLY_ROWS, TALLY_DTYPE)
+        assert out.dtype == TALLY_DTYPE and out.shape == (TALLY_ROWS,)
+        st = self._L.rl_tally_batch(self._h, permits.shape[0], _p(permits), _p(limiter), _p(ops),
+                                    _p(allowed), _p(remaining), _p(out), flags)
+        if st != RL_OK:
+            raise RlError(st, "rl_tally_batch")
+        return out
+
+    def tally_batch_device(self, n, permits, limiter, ops, allowed, remaining, out, accumulate=False,
+                           stream=None):
+        """rl_tally_batch_device on device buffers (torch tensors or raw pointers; limiter and ops
+        may be None); `out` is a device buffer of TALLY_ROWS x 96 bytes, 8-byte aligned.
+        Asynchronous, ordered behind the batches submitted before it."""
+        st = self._L.rl_tally_batch_device(self._h, int(n), _p(permits), _p(limiter), _p(ops), _p(allowed),
+                                           _p(remaining), _p(out), TALLY_ACCUMULATE if accumulate else 0,
+                                           _p(stream))
+        if st != RL_OK:
+            raise RlError(st, "rl_tally_batch_device")
+
+    def top_denied(self, keys, permits, limiter, ops, allowed, remaining, sel_limiter, k, min_count):
+        """The keys of a finished host batch denied at least min_count times under limiter
+        sel_limiter, the k most often denied first (rl_top_denied; order as top_keys). Returns
+        (keys uint64, counts uint64, n_heavy, n_denied); raises RlError(RL_E_CAPACITY) when the
+        denied keys overflow the candidate store. Read-only."""
+        keys = np.ascontiguousarray(keys, np.uint64)
+        permits = np.ascontiguousarray(permits, np.int32)
+        limiter = None if limiter is None else np.ascontiguousarray(limiter, np.uint16)
+        ops = None if ops is None else np.ascontiguousarray(ops, np.uint8)
+        allowed = np.ascontiguousarray(allowed, np.uint8)
+        remaining = np.ascontiguousarray(remaining, np.int64)
+        k, n = int(k), keys.shape[0]
+        top = np.zeros(max(min(k, TOP_KEYS_MAX), 0), np.uint64)
+        cnt = np.zeros_like(top)
+        n_out = ctypes.c_size_t(0)
+        n_heavy, n_denied = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        st = self._L.rl_top_denied(self._h, n, _p(keys) if n else None, _p(permits), _p(limiter), _p(ops),
+                                   _p(allowed), _p(remaining), int(sel_limiter), k, int(min_count),
+                                   _p(top), _p(cnt), ctypes.byref(n_out), ctypes.byref(n_heavy),
+                                   ctypes.byref(n_denied))
+        if st != RL_OK:
+            raise RlError(st, "rl_top_denied")
+        return top[:n_out.value], cnt[:n_out.value], n_heavy.value, n_denied.value
+
+    def top_denied_device(self, n, keys, permits, limiter, ops, allowed, remaining, sel_limiter, k,
+                          min_count, stream=None):
+        """rl_top_denied_device on device tensors (limiter and ops may be None). Returns (keys,
+        counts, n_heavy, n_denied) as top_keys_device does: two device tensors of n_out 64-bit
+        words (torch.uint64 views) and two ints; reads the header back, so it synchronises.
+        Raises RlError(RL_E_CAPACITY) on overflow."""
+        import torch
+        k = int(k)
+        dev = allowed.device
+        top = torch.zeros(max(min(k, TOP_KEYS_MAX), 1), dtype=torch.int64, device=dev)
+        cnt = torch.zeros_like(top)
+        hdr = torch.zeros(4, dtype=torch.int64, device=dev)
+        st = self._L.rl_top_denied_device(self._h, int(n), _p(keys) if n else None, _p(permits),
+                                          _p(limiter), _p(ops), _p(allowed), _p(remaining),
+                                          int(sel_limiter), k, int(min_count), _p(top), _p(cnt), _p(hdr),
+                                          _p(stream))
+        if st != RL_OK:
+            raise RlError(st, "rl_top_denied_device")
+        self.sync()
+        n_out, n_heavy, overflow, n_denied = (int(x) for x in hdr.cpu())
+        if overflow:
+            raise RlError(RL_E_CAPACITY, "rl_top_denied_device")
+        return top[:n_out].view(torch.uint64), cnt[:n_out].view(torch.uint64), n_heavy, n_denied
 
     def limiter_usage(self, limiter, now_ns) -> dict:
         """Census of one limiter's table at now_ns (rl_limiter_usage): a dict of the rl_usage

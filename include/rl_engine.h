@@ -273,7 +273,7 @@ int  rl_retry_after_device(rl_engine* e, size_t n, const uint64_t* key_hash,
  * min_count or sample less).
  * Both forms only read: no limiter state, batch statistic or rl_last_status changes. Their
  * scratch (38.8 MiB, whatever n is) is allocated by the first call and freed by rl_destroy.
- * One top-keys call may be in flight per engine.
+ * One top-keys call (or top-denied call, below: the same scratch) may be in flight per engine.
  * The host form stages key_hash through the engine's staging buffers in chunks of at most
  * rl_opts.max_batch keys (n itself is not bounded by it) and synchronises. */
 #define RL_TOP_KEYS_MAX        4096    /* = the owner directory's capacity                */
@@ -287,6 +287,76 @@ int  rl_top_keys(rl_engine* e, size_t n, const uint64_t* key_hash, uint32_t k, u
 int  rl_top_keys_device(rl_engine* e, size_t n, const uint64_t* key_hash, uint32_t k,
                         uint64_t min_count, uint64_t* top_key, uint64_t* top_count, uint64_t* hdr,
                         void* stream);
+
+/* ---- batch report: per-limiter counts and the keys being throttled ----------------
+ * Two read-only analyses of a FINISHED batch's own arrays: what the caller submitted
+ * (permits, limiter, op) and what the engine answered (allowed, remaining). `limiter` and `op`
+ * may be NULL (limiter 0, RL_OP_ACQUIRE), as in the batch calls. With L the engine's limiter
+ * count, request i has
+ *   row   = limiter[i] < L ? limiter[i] : RL_TALLY_UNKNOWN   (ids are 0..254, so row 255 is free)
+ *   class = the first that matches of
+ *     INVALID  limiter[i] >= L, or op[i] > 2, or op[i] == RL_OP_ACQUIRE and permits[i] <= 0
+ *              (the engine's own rule, taken from the inputs: a token bucket's remaining can
+ *              legitimately read -2 after a time regression)
+ *     ERROR    allowed[i] == 0 and remaining[i] == RL_REMAINING_ERROR
+ *     PEEK / RESET  by op[i]
+ *     ALLOWED  allowed[i] != 0
+ *     DENIED   otherwise; those with remaining[i] == RL_REMAINING_UNKNOWN (token bucket,
+ *              permits > maxPermits; a rejection in TokenBucketRateLimiter.java:114) are also
+ *              counted in over_max.
+ * One ambiguity is inherited from the result encoding: a valid, denied token-bucket acquire whose
+ * balance reads exactly -3 after a time regression is counted as ERROR.
+ * A row's `allowed` / `denied` are the reference's meters ratelimiter.requests.allowed /
+ * .rejected (sliding window) and ratelimiter.tokenbucket.allowed / .rejected (token bucket) of
+ * that limiter for this batch.
+ *
+ * rl_tally_batch: out[RL_TALLY_ROWS], one rl_limiter_tally per row; every row satisfies
+ * requests == invalid + errors + allowed + denied + peeks + resets. Without RL_TALLY_ACCUMULATE
+ * all 256 rows are overwritten (zeros included, reserved = 0); with it the batch's counts are
+ * added to what `out` holds (reserved is left alone), so an exporter can keep cumulative
+ * counters on the device and read 24 KB per scrape. All sums are modulo 2^64.
+ * The device form is enqueued on `stream` (NULL = the engine's stream) behind every batch
+ * submitted before it, without a host synchronisation, and returns argument / launch status
+ * only; `out` is DEVICE memory, 8-byte aligned. The host form stages the arrays through the
+ * engine's staging buffers in pieces of at most rl_opts.max_batch requests (n itself is not
+ * bounded by it) and synchronises. Neither form changes limiter state, cache words,
+ * rl_batch_stats or the status rl_last_status reports, and neither collects that status.
+ * RL_E_INVALID_ARG, before any device call and with `out` untouched: a null engine, n > 0 with
+ * a null permits / allowed / remaining, a null out, unknown flag bits, a device `out` that is
+ * not 8-byte aligned. n == 0 is valid. RL_E_TOO_LARGE: n > 2^31 in the device form. */
+#define RL_TALLY_ROWS       256
+#define RL_TALLY_UNKNOWN    255
+#define RL_TALLY_ACCUMULATE 0x1u
+typedef struct rl_limiter_tally {   /* 96 bytes */
+    uint64_t requests, invalid, errors, allowed, denied, over_max, peeks, resets;
+    uint64_t permits_allowed;       /* sum of permits over ALLOWED */
+    uint64_t permits_denied;        /* sum of permits over DENIED  */
+    uint64_t reserved[2];           /* written as 0 */
+} rl_limiter_tally;
+int  rl_tally_batch(rl_engine* e, size_t n, const int32_t* permits, const uint16_t* limiter,
+                    const uint8_t* op, const uint8_t* allowed, const int64_t* remaining,
+                    rl_limiter_tally* out, uint32_t flags);
+int  rl_tally_batch_device(rl_engine* e, size_t n, const int32_t* permits, const uint16_t* limiter,
+                           const uint8_t* op, const uint8_t* allowed, const int64_t* remaining,
+                           rl_limiter_tally* out, uint32_t flags, void* stream);
+/* rl_top_denied: who is being throttled. With S = { i : row(i) == sel_limiter and class(i) ==
+ * DENIED }, the result is exactly what rl_top_keys defines for the subsequence key_hash[S]: the
+ * same order (count descending, then key ascending unsigned), n_heavy / n_out, untouched
+ * tails, overflow rule and RL_E_CAPACITY behaviour, and the same k / min_count / n argument
+ * checks; n > 0 also needs permits, allowed and remaining, and sel_limiter >= L is
+ * RL_E_INVALID_ARG. The device form's hdr = { n_out, n_heavy, overflow, |S| }; the host form
+ * returns |S| in *n_denied (nullable). Call rules as rl_top_keys(_device). Both forms use the
+ * top-keys scratch: one top-keys OR top-denied call may be in flight per engine. */
+int  rl_top_denied(rl_engine* e, size_t n, const uint64_t* key_hash, const int32_t* permits,
+                   const uint16_t* limiter, const uint8_t* op, const uint8_t* allowed,
+                   const int64_t* remaining, uint16_t sel_limiter, uint32_t k, uint64_t min_count,
+                   uint64_t* top_key, uint64_t* top_count, size_t* n_out, uint64_t* n_heavy,
+                   uint64_t* n_denied);
+int  rl_top_denied_device(rl_engine* e, size_t n, const uint64_t* key_hash, const int32_t* permits,
+                          const uint16_t* limiter, const uint8_t* op, const uint8_t* allowed,
+                          const int64_t* remaining, uint16_t sel_limiter, uint32_t k,
+                          uint64_t min_count, uint64_t* top_key, uint64_t* top_count, uint64_t* hdr,
+                          void* stream);
 
 /* Observability. */
 int  rl_batch_stats_get(rl_engine* e, rl_batch_stats* out);
