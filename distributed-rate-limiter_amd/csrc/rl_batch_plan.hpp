@@ -68,7 +68,7 @@ inline int plan_batch(const BatchTune& t, size_t n, uint32_t n_regions, BatchPla
     p.passes = p.bitsP <= kMaxDigitBits ? 1 : 2;
     if (p.bitsP > 2 * kMaxDigitBits) return RL_E_LIMITERS;
     // Two passes: pass 0 partitions by the high dh bits of the region id (2^dh bins of 2^s0
-    // consecutive regions), then k_group groups each bin by region locally (rl_partition.hip)
+    // consecutive regions), then rl_group.hip groups each bin by region locally
     p.dh = p.passes == 1 ? p.bitsP
                          : std::max(p.bitsP - kMaxDigitBits, std::min<int>((int)t.group_bits, kMaxDigitBits));
     p.s0 = p.bitsP - p.dh;

@@ -174,7 +174,7 @@ static int run_batch_device(rl_engine* e, size_t n, const uint64_t* key, const i
         pa.route_list = r_list; pa.lo_bins = 1u << dh; pa.rec_out_route = B.rec1;
         pa.digit = B.digit;
     }
-    HIP_OK(launch_upsweep(pa, true, wide, ps));
+    HIP_OK(launch_upsweep(pa, ps));
     mark_on(e, ps, 1);
     HIP_OK(launch_scan_rows(B.counts, B.counts, nb0, nt, B.bin_total, ps));
     HIP_OK(launch_scan_small(B.bin_total, B.bin_base, nb0, ps));
@@ -185,7 +185,7 @@ static int run_batch_device(rl_engine* e, size_t n, const uint64_t* key, const i
         pa.seg_adj = B.seg; pa.n_segs = n_segs; pa.seg_tiles = P.seg_tiles;
     }
     mark_on(e, ps, 2);
-    HIP_OK(launch_scatter(pa, true, wide, ps));
+    HIP_OK(launch_scatter(pa, wide, ps));
     if (route)
         HIP_OK(launch_route_ranges(r_list, B.bin_base, B.bin_total, 1u << dh, r_start, r_cnt,
                                    B.d_ctl, ps));

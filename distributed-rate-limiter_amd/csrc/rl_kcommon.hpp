@@ -1,7 +1,8 @@
 // rl_kcommon.hpp — device helpers shared by the kernel translation units.
 //
-// The batched rate-limit decision pipeline for gfx950 (MI355X): rl_partition.hip,
-// rl_region.hip, rl_hot.hip, rl_misc.hip share this header.
+// The batched rate-limit decision pipeline for gfx950 (MI355X): rl_partition.hip (steps 1-3),
+// rl_group.hip (the local grouping of two-pass batches), the region and hot-chain units
+// (rl_rt_*.hip, rl_hot.hip: step 4), rl_unpermute.hip (step 5) and rl_misc.hip share this header.
 //
 // One batch = requests in arrival order. The pipeline groups every request with
 // the other requests of its (limiter, key) WITHOUT a full sort:
@@ -12,8 +13,8 @@
 //   2. k_scan_rows/k_scan_small : exclusive scan of the [bin][tile] histogram.
 //   3. k_scatter  : stable partition (wave ballot-match ranking) of the requests
 //                   into bin order, packed into 16-byte records.
-//   (more than 8192 regions: pass 0 partitions by the region's high digit and k_group
-//    then groups each pass-0 bin by region locally.)
+//   (more than 8192 regions: pass 0 partitions by the region's high digit and k_gtiles /
+//    k_gcount / k_gscan / k_gplace(_lds) then group each pass-0 bin by region locally.)
 //   4. k_regions  : one single-wave workgroup per REGION. The wave loads its region's
 //                   256 state slots (8 KB) into LDS once (or faults in single buckets of
 //                   a sparse region), streams the region's records in arrival order and
@@ -177,11 +178,19 @@ struct LimLds {
     uint8_t bits[256];
 };
 
-__device__ inline void load_lim_lds(LimLds& L, const PartArgs& a) {
-    for (uint32_t l = threadIdx.x; l < a.n_lim; l += blockDim.x) {
-        L.base[l] = a.lims[l].region_base;
-        L.bits[l] = (uint8_t)a.lims[l].region_bits;
+__device__ inline void load_lim_lds(LimLds& L, const DevLimiter* lims, uint32_t n_lim) {
+    for (uint32_t l = threadIdx.x; l < n_lim; l += blockDim.x) {
+        L.base[l] = lims[l].region_base;
+        L.bits[l] = (uint8_t)lims[l].region_bits;
     }
+}
+// Region (= global bin) of the key hash h of limiter lim, and of a record.
+__device__ inline uint32_t region_of(const LimLds& L, uint64_t h, uint32_t lim, int32_t shard_bits) {
+    return L.base[lim] + region_local(h, shard_bits, L.bits[lim]);
+}
+template <class Codec>
+__device__ inline uint32_t region_of_rec(const LimLds& L, const typename Codec::Rec& r, int32_t shard_bits) {
+    return region_of(L, r.h, Codec::limiter_of(r), shard_bits);
 }
 
 // Tile processed by this workgroup at iteration `it` of a persistent grid: the
@@ -198,21 +207,17 @@ __device__ inline uint32_t cursor_base(const PartArgs& a, uint32_t b, uint32_t t
     return a.seg_adj ? a.seg_adj[b * a.n_segs + tile / a.seg_tiles] : a.bin_base[b];
 }
 
-// Global bin id of element i (pass 0: raw arrays; later passes: records).
-template <class Codec, bool RAW>
+// Bins of this partition pass.
+__host__ __device__ inline uint32_t pass_bins(const PartArgs& a) {
+    return a.n_bins_pass ? a.n_bins_pass : 1u << a.digit_bits;
+}
+
+// Global bin id (the region) of request i.
 __device__ inline uint32_t bin_of(const PartArgs& a, uint32_t i, const LimLds& L) {
-    uint64_t h;
-    uint32_t lim;
-    if constexpr (RAW) {
-        h = mix64(ld<kNtUp>(a.key + i));
-        lim = a.limiter ? a.limiter[i] : 0u;
-        if (lim >= a.n_lim) lim = 0;  // invalid: routed to limiter 0's region, rejected there
-    } else {
-        const typename Codec::Rec* r = (const typename Codec::Rec*)a.rec_in + i;
-        h = r->h;
-        lim = Codec::limiter_of(*r);
-    }
-    return L.base[lim] + region_local(h, a.shard_bits, L.bits[lim]);
+    const uint64_t h = mix64(ld<kNtUp>(a.key + i));
+    uint32_t lim = a.limiter ? a.limiter[i] : 0u;
+    if (lim >= a.n_lim) lim = 0;  // invalid: routed to limiter 0's region, rejected there
+    return region_of(L, h, lim, a.shard_bits);
 }
 
 // Routed regions (pass 0): the route table (kRouteSlots region ids) in LDS; a region is
@@ -235,7 +240,7 @@ __device__ inline uint32_t route_find(const RouteLds& R, uint32_t b) {
     return k1 == b ? s1 : k2 == b ? s2 : kNone;
 }
 // Partition digit of global bin g (a region id) in pass 0: routed region -> lo_bins + its dense index,
-// else its high digit g >> digit_shift (two-pass batches: k_group then groups each of
+// else its high digit g >> digit_shift (two-pass batches: rl_group.hip then groups each of
 // those bins by region; one-pass batches: digit_shift 0, the region itself).
 __device__ inline uint32_t pass_digit(const PartArgs& a, uint32_t g, const RouteLds& R) {
     if (a.route_list) {

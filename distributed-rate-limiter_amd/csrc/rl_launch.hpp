@@ -57,15 +57,13 @@ struct BatchCtl {
 constexpr uint32_t kGrowUsed = 208;
 
 struct PartArgs {
-    // pass 0 reads the caller's SoA request arrays
+    // the caller's SoA request arrays
     const uint64_t* key;
     const int32_t* permits;
     const int64_t* now_ns;
     const uint16_t* limiter;   // nullable
     const uint8_t* op;         // nullable
-    // later passes read records
-    const void* rec_in;
-    void* rec_out;
+    void* rec_out;             // records in bin order
     uint32_t* pos_out;         // pos_out[i] = destination of element i
     uint32_t n;
     uint32_t n_tiles;
@@ -100,7 +98,6 @@ struct PartArgs {
     uint32_t lo_bins;
     void* rec_out_route;
     uint16_t* digit;           // [n]: pass-0 digit per request (routing only)
-    const uint32_t* n_dev;     // pass 1: records to partition, on device (the normal ones)
 };
 
 struct HotInfo;
@@ -434,13 +431,11 @@ hipError_t launch_shrink_merge(const Slot* src_tab, const uint64_t* src_x, Slot*
                                uint64_t* dst_x, uint64_t n_dst, uint32_t s, const DevLimiter& L,
                                int64_t now_ms, bool live_only, uint32_t* fail, hipStream_t st);
 
-hipError_t launch_upsweep(const PartArgs& a, bool raw, bool wide, hipStream_t s);
-hipError_t launch_scatter(const PartArgs& a, bool raw, bool wide, hipStream_t s);
+hipError_t launch_upsweep(const PartArgs& a, hipStream_t s);
+hipError_t launch_scatter(const PartArgs& a, bool wide, hipStream_t s);
 hipError_t launch_scan_rows(const uint32_t* in, uint32_t* out, uint32_t rows, uint32_t cols,
                             uint32_t* totals, hipStream_t s);
 hipError_t launch_scan_small(const uint32_t* in, uint32_t* out, uint32_t len, hipStream_t s);
-hipError_t launch_add_rows(const uint32_t* row_base, uint32_t* data, uint32_t rows,
-                           uint32_t cols, hipStream_t s);
 // The hot chains (k_hot_chains) on the side stream hs after event e0 on s, launched before
 // the region-order and solo kernels so that their single waves (one SIMD's registers each)
 // are dispatched ahead of the normal regions' ~10^6 waves; launch_region then runs the

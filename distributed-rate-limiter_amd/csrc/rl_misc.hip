@@ -1,4 +1,5 @@
-// rl_misc.hip — synthetic traces, multi-GPU routing kernels, status kernels.
+// rl_misc.hip — synthetic traces, multi-GPU routing kernels, status kernels, the region
+// stage's batch counters (k_stats_reduce).
 #include "rl_kcommon.hpp"
 
 #pragma clang fp contract(off)
@@ -505,6 +506,38 @@ __global__ void k_status_accum(const BatchCtl* ctl, unsigned long long flags, un
 hipError_t launch_status_accum(const BatchCtl* ctl, unsigned long long flags, unsigned long long* acc,
                                hipStream_t s) {
     hipLaunchKernelGGL(k_status_accum, dim3(1), dim3(64), 0, s, ctl, flags, acc);
+    return hipGetLastError();
+}
+
+// Fold the sharded batch counters into BatchCtl and clear them for the next batch.
+__global__ __launch_bounds__(256) void k_stats_reduce(unsigned long long* stats, BatchCtl* ctl) {
+    __shared__ unsigned long long part[kStWords][4];
+    const uint32_t t = threadIdx.x, lane = t & 63, wid = t >> 6;
+    unsigned long long acc[kStCount] = {};
+    for (uint32_t s = t; s < kStatSlots; s += 256) {
+        unsigned long long* p = stats + (size_t)s * kStWords;
+#pragma unroll
+        for (int k = 0; k < (int)kStCount; ++k) { acc[k] += p[k]; p[k] = 0; }
+    }
+#pragma unroll
+    for (int k = 0; k < (int)kStCount; ++k) {
+        unsigned long long v = acc[k];
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (lane == 0) part[k][wid] = v;
+    }
+    __syncthreads();
+    if (t < kStCount) {
+        const unsigned long long v = part[t][0] + part[t][1] + part[t][2] + part[t][3];
+        unsigned long long* dst = t == kStAllowed ? &ctl->allowed : t == kStInvalid ? &ctl->invalid
+                                : t == kStCapErr ? &ctl->cap_err : t == kStDistinct ? &ctl->distinct
+                                : t == kStRegions ? &ctl->regions : t == kStCacheHits ? &ctl->cache_hits
+                                : &ctl->table_bytes;
+        *dst += v;
+    }
+}
+
+hipError_t launch_stats_reduce(unsigned long long* stats, BatchCtl* ctl, hipStream_t s) {
+    hipLaunchKernelGGL(k_stats_reduce, dim3(1), dim3(256), 0, s, stats, ctl);
     return hipGetLastError();
 }
 

@@ -1,44 +1,63 @@
-// rl_partition.hip — stable partition of a batch into region order (upsweep, scans,
-// scatter, bin bounds) and the unpermute back to arrival order, for gfx950.
+// rl_partition.hip — stable partition of a batch's requests into bin order (upsweep, scans,
+// the two scatters, segment bases, routed ranges), for gfx950. Every pass reads the caller's
+// request arrays; a two-pass batch's bins are then grouped by region in rl_group.hip.
 #include "rl_kcommon.hpp"
 
 #pragma clang fp contract(off)
 
 namespace rl {
 
+// Dynamic LDS of the kernels below; the kernels carve their pointers, and the launchers size
+// the launch, with the same functions.
+// k_upsweep: hist[bins] u32, then the route table when routing.
+__host__ __device__ inline size_t upsweep_lds_bytes(uint32_t bins, bool route) {
+    return bins * sizeof(uint32_t) + (route ? sizeof(RouteLds) : 0);
+}
+// k_scatter: cntw[bins] u64 (a bin's per-wave counts of the round, one byte each), cur[bins] u32
+// (its next slot).
+__host__ __device__ inline size_t scatter_lds_bytes(uint32_t bins) {
+    return bins * (sizeof(uint64_t) + sizeof(uint32_t));
+}
+// k_scatter_split: the same, then from the next 16-B boundary stg[2][kTileThreads] records and
+// sdg[2][kTileThreads] u16 digits (the two stages).
+__host__ __device__ inline size_t scatter_stage_off(uint32_t bins) {
+    return (scatter_lds_bytes(bins) + 15) & ~(size_t)15;
+}
+template <class Codec>
+__host__ __device__ inline size_t scatter_split_lds_bytes(uint32_t bins) {
+    return scatter_stage_off(bins) + 2 * kTileThreads * (sizeof(typename Codec::Rec) + sizeof(uint16_t));
+}
+
 // ------------------------------------------------------------------ 1. upsweep
 // DIG: the pass stores each element's digit for the scatter (routing).
-template <class Codec, bool RAW, bool DIG>
+template <bool DIG>
 __global__ __launch_bounds__(kTileThreads) void k_upsweep(PartArgs a) {
     // dynamic LDS (upsweep_lds_bytes): the histogram of this pass's bins, then the route table
     // when routing; sized to the pass so that 4 workgroups fit a CU at 8192 bins
     extern __shared__ uint32_t dyn_lds[];
     __shared__ LimLds L;
     const uint32_t t = threadIdx.x;
-    const uint32_t bins = a.n_bins_pass ? a.n_bins_pass : 1u << a.digit_bits;
+    const uint32_t bins = pass_bins(a);
     uint32_t* hist = dyn_lds;
-    RouteLds& R = *(RouteLds*)(dyn_lds + bins);
-    load_lim_lds(L, a);
+    RouteLds& R = *(RouteLds*)((char*)dyn_lds + upsweep_lds_bytes(bins, false));
+    load_lim_lds(L, a.lims, a.n_lim);
     if (a.route_list) route_load(R, a.route_list);
-    if constexpr (RAW) {
-        if (blockIdx.x == 0 && t == 0) {
-            BatchCtl* c = a.ctl;
-            c->base_ms = floor_div_ms(a.now_ns[0]) - (1LL << 31);
-            c->min_now_key = ~0ULL;
-            c->max_now_key = 0;
-            c->span_overflow = 0;
-            c->n_esc = 0;
-            c->allowed = c->distinct = c->invalid = c->cap_err = c->regions = c->cache_hits = 0;
-            c->grow[0] = c->grow[1] = c->grow[2] = c->grow[3] = 0;
-            c->table_bytes = 0;
-            c->n_normal = a.n;                           // k_route_ranges lowers it when routing
-            c->n_hot = 0;                                // k_hot_prep sets it when the hot path runs
-            c->internal_err = 0;
-            c->n_walk = 0;                               // k_hot_scan sets it when the hot path runs
-        }
+    if (blockIdx.x == 0 && t == 0) {
+        BatchCtl* c = a.ctl;
+        c->base_ms = floor_div_ms(a.now_ns[0]) - (1LL << 31);
+        c->min_now_key = ~0ULL;
+        c->max_now_key = 0;
+        c->span_overflow = 0;
+        c->n_esc = 0;
+        c->allowed = c->distinct = c->invalid = c->cap_err = c->regions = c->cache_hits = 0;
+        c->grow[0] = c->grow[1] = c->grow[2] = c->grow[3] = 0;
+        c->table_bytes = 0;
+        c->n_normal = a.n;                           // k_route_ranges lowers it when routing
+        c->n_hot = 0;                                // k_hot_prep sets it when the hot path runs
+        c->internal_err = 0;
+        c->n_walk = 0;                               // k_hot_scan sets it when the hot path runs
     }
-    // later passes partition the normal records only (their count is on device)
-    const uint32_t n = a.n_dev ? *a.n_dev : a.n;
+    const uint32_t n = a.n;
     for (uint32_t it = 0;; ++it) {
         const uint32_t tile = tile_at(it, a.n_tiles);
         if (tile >= a.n_tiles) break;
@@ -50,7 +69,7 @@ __global__ __launch_bounds__(kTileThreads) void k_upsweep(PartArgs a) {
             for (uint32_t r = 0; r < items; ++r) {
                 const uint32_t i = tile * T + r * (uint32_t)kTileThreads + t;
                 if (i < n) {
-                    const uint32_t g = bin_of<Codec, RAW>(a, i, L);
+                    const uint32_t g = bin_of(a, i, L);
                     const uint32_t d = pass_digit(a, g, R);
                     atomicAdd(&hist[d], 1u);
                     if constexpr (DIG) a.digit[i] = (uint16_t)d;      // the scatter reads it back
@@ -103,23 +122,15 @@ __global__ __launch_bounds__(1024) void k_scan_small(const uint32_t* in, uint32_
     }
 }
 
-__global__ __launch_bounds__(256) void k_add_rows(const uint32_t* row_base, uint32_t* data,
-                                                  uint32_t cols) {
-    const size_t row = blockIdx.x;
-    const uint32_t b = row_base[row];
-    for (uint32_t k = threadIdx.x; k < cols; k += 256) data[row * cols + k] += b;
-}
-
 // ------------------------------------------------------------------ 3. scatter
 // Stable: a tile's elements are ranked in (round, wave, lane) order, which is the
 // arrival order; tiles are ordered by the exclusive [bin][tile] scan. The inputs of
 // round r+1 are loaded into registers before round r is ranked, so the global-load
 // latency hides behind the two LDS barriers of a round.
-template <class Codec, bool RAW>
-struct ScatterIn;
-
-template <class Codec>
-struct ScatterIn<Codec, true> {
+//
+// One request's inputs. They are passed by const& into inlined code and never copied: a
+// register move would wait on its load.
+struct ScatterIn {
     uint64_t key; int64_t now_ns; int32_t permits; uint32_t lim; uint32_t op; uint32_t dig;
     // Every load is unconditional (an absent array reads the key's bytes instead and the
     // value is dropped): a load under a branch leaves the wait-count pass unsure how many
@@ -141,13 +152,99 @@ struct ScatterIn<Codec, true> {
     __device__ inline uint32_t dig_v(const PartArgs& a) const { return a.digit ? dig : 0u; }
 };
 
-template <class Codec>
-struct ScatterIn<Codec, false> {
-    typename Codec::Rec rec;
-    __device__ inline void load(const PartArgs& a, uint32_t i) {
-        rec = ((const typename Codec::Rec*)a.rec_in)[i];
+// Earliest / latest now_ms of a workgroup's valid requests and whether one of them leaves the
+// compact record's span, published to BatchCtl once per workgroup.
+struct TimeRange {
+    uint64_t mn = ~0ULL, mx = 0;
+    bool overflow = false;
+    template <class Codec>
+    __device__ __forceinline__ void add(int64_t now_ms, int64_t base) {
+        // only the compact record keeps now relative to base
+        if constexpr (std::is_same<Codec, CodecC>::value) {
+            const int64_t rel = now_ms - base;
+            overflow |= rel < 0 || rel > 0xFFFFFFFFLL;
+        }
+        const uint64_t k = ord_key(now_ms);
+        mn = k < mn ? k : mn;
+        mx = k > mx ? k : mx;
+    }
+    // (every thread of the workgroup's WAVES waves) -> one atomic each
+    template <int WAVES>
+    __device__ __forceinline__ void publish(BatchCtl* ctl, uint64_t (&s_mm)[2][WAVES]) {
+        const uint32_t t = threadIdx.x, lane = t & 63, wid = t >> 6;
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint64_t a1 = __shfl_xor(mn, o, 64), b1 = __shfl_xor(mx, o, 64);
+            mn = a1 < mn ? a1 : mn;
+            mx = b1 > mx ? b1 : mx;
+        }
+        __syncthreads();
+        if (lane == 0) { s_mm[0][wid] = mn; s_mm[1][wid] = mx; }
+        const bool any_over = __syncthreads_or(overflow);
+        if (t == 0) {
+            for (int w = 1; w < WAVES; ++w) {
+                mn = s_mm[0][w] < mn ? s_mm[0][w] : mn;
+                mx = s_mm[1][w] > mx ? s_mm[1][w] : mx;
+            }
+            if (mn != ~0ULL) atomicMin((unsigned long long*)&ctl->min_now_key, (unsigned long long)mn);
+            if (mx != 0) atomicMax((unsigned long long*)&ctl->max_now_key, (unsigned long long)mx);
+            if (any_over) atomicOr(&ctl->span_overflow, 1u);
+        }
     }
 };
+
+// Request i's record and its digit of this pass (a zero record, digit 0, past the batch).
+template <class Codec>
+__device__ __forceinline__ void encode_request(const PartArgs& a, const LimLds& L, int64_t base,
+                                               const ScatterIn& in, uint32_t i, uint32_t n,
+                                               TimeRange& tr, typename Codec::Rec& rec, uint32_t& d) {
+    rec = typename Codec::Rec{};
+    d = 0;
+    if (i >= n) return;
+    uint32_t lim = in.lim_v(a), op = in.op_v(a);
+    const int32_t p = in.permits;
+    const int64_t now_ms = floor_div_ms(in.now_ns);
+    const bool lim_ok = lim < a.n_lim;
+    if (!lim_ok) lim = 0;
+    const bool invalid = !lim_ok || op > 2u || (op == 0u && p <= 0);
+    if (op > 2u) op = 0;
+    const uint64_t h = mix64(in.key);
+    rec = Codec::enc(h, now_ms, base, p, op, lim, invalid);
+    // an invalid request's now is never read: it neither widens the batch's time range nor
+    // rejects the batch for its span
+    if (!invalid) tr.add<Codec>(now_ms, base);
+    // routing: the upsweep's digit (route-table lookup done once per request)
+    d = a.digit ? in.dig_v(a)
+                : (region_of(L, h, lim, a.shard_bits) >> a.digit_shift) & ((1u << a.digit_bits) - 1);
+}
+
+// One round's ranks: the position of this lane's element of bin d (active lanes), from the
+// bin's next slot cur[d], the earlier waves' counts of the round (cntw[d]: the waves' bytes
+// packed in one word, so a lane sums them with one read and two v_sad_u8) and the lane's rank
+// among its own wave's elements of the bin (ballot match). Called by all waves `wid` of a
+// ranking group together (two barriers); cur[d] moves past the round. no_match / no_barrier:
+// the measurement-only variants (ranks then wrong), constants in the product kernels.
+__device__ __forceinline__ uint32_t rank_round(uint64_t* cntw, uint32_t* cur, uint32_t d, int digit_bits,
+                                               bool active, uint32_t lane, uint32_t wid,
+                                               bool no_match, bool no_barrier) {
+    const uint64_t m = no_match ? (1ULL << lane) : wave_match(d, digit_bits, active);
+    const uint32_t lr = popc_below(m);
+    const uint32_t cnt = (uint32_t)__popcll(m);
+    const bool leader = active && lr == 0;
+    if (leader) ((uint8_t*)&cntw[d])[wid] = (uint8_t)cnt;
+    if (!no_barrier) __syncthreads();
+    uint32_t pos = 0;
+    if (active) {
+        const uint64_t below = wid == 0 ? 0ULL : cntw[d] & ((1ULL << (8 * wid)) - 1);
+        pos = cur[d] + lr + __builtin_amdgcn_sad_u8((uint32_t)below, 0u, 0u) +
+              __builtin_amdgcn_sad_u8((uint32_t)(below >> 32), 0u, 0u);
+    }
+    if (!no_barrier) __syncthreads();
+    if (leader) {
+        atomicAdd(&cur[d], cnt);
+        ((uint8_t*)&cntw[d])[wid] = 0;
+    }
+    return pos;
+}
 
 // The record output arrays: routed regions' records go straight to the final array, at a
 // uniform element offset from the normal one. Selecting between the two kernel-argument
@@ -165,34 +262,27 @@ __device__ inline void scatter_outputs(const PartArgs& a, Rec*& out_norm, int64_
 
 constexpr int kScatterDepth = 8;   // rounds of inputs in flight (divides tile_items)
 
-template <class Codec, bool RAW>
+template <class Codec>
 __global__ __launch_bounds__(kTileThreads) void k_scatter(PartArgs a) {
     using Rec = typename Codec::Rec;
     static_assert(kTileThreads / 64 <= 8, "per-wave counts are packed 8 to a bin");
-    // dynamic LDS (scatter_lds_bytes): per bin, this round's per-wave counts packed in one
-    // word (cntw), then the next slot (cur); sized to the pass's bins
-    extern __shared__ uint64_t dyn_lds64[];
-    // this round's count of each wave per bin, the waves' bytes packed in one word: a lane
-    // sums the earlier waves' counts for its bin with one read and two v_sad_u8
+    extern __shared__ uint64_t dyn_lds64[];           // (scatter_lds_bytes)
     __shared__ LimLds L;
     __shared__ uint64_t s_mm[2][kTileThreads / 64];
     const uint32_t t = threadIdx.x, lane = t & 63, wid = t >> 6;
-    const uint32_t bins = a.n_bins_pass ? a.n_bins_pass : 1u << a.digit_bits;
+    const uint32_t bins = pass_bins(a);
     uint64_t* cntw = dyn_lds64;
-    uint32_t* cur = (uint32_t*)(dyn_lds64 + bins);
-    load_lim_lds(L, a);
-    int64_t base = 0;
-    if constexpr (RAW) base = a.ctl->base_ms;
-    // later passes partition the normal records only (their count is on device); lanes past
-    // it store to the padding past the whole batch (a.n), clear of the routed records
-    const uint32_t n = a.n_dev ? *a.n_dev : a.n;
+    uint32_t* cur = (uint32_t*)(cntw + bins);
+    load_lim_lds(L, a.lims, a.n_lim);
+    const int64_t base = a.ctl->base_ms;
+    // lanes past the batch store to the padding past it (a.n)
+    const uint32_t n = a.n;
     const uint32_t last = n - 1;
     Rec* out_norm;
     int64_t route_off;
     uint32_t lo_route;
     scatter_outputs(a, out_norm, route_off, lo_route);
-    uint64_t mn = ~0ULL, mx = 0;
-    bool overflow = false;
+    TimeRange tr;
     for (uint32_t it = 0;; ++it) {
         const uint32_t tile = tile_at(it, a.n_tiles);
         if (tile >= a.n_tiles) break;
@@ -205,66 +295,19 @@ __global__ __launch_bounds__(kTileThreads) void k_scatter(PartArgs a) {
         }
         // kScatterDepth rounds of inputs in flight; out-of-range lanes re-load element n-1
         // so every wave issues the same loads and stores each round (static vmcnt counting)
-        ScatterIn<Codec, RAW> in[kScatterDepth];
+        ScatterIn in[kScatterDepth];
 #pragma unroll
         for (int k = 0; k < kScatterDepth; ++k) in[k].load(a, min(tile0 + (uint32_t)k * kTileThreads + t, last));
         __syncthreads();
-        auto round = [&](const ScatterIn<Codec, RAW>& in, int r) {
+        auto round = [&](const ScatterIn& in, int r) {
             const uint32_t i = tile0 + (uint32_t)r * kTileThreads + t;
             const bool active = i < n;
-            Rec rec{};
-            uint32_t d = 0;
-            if (active) {
-                if constexpr (RAW) {
-                    uint32_t lim = in.lim_v(a), op = in.op_v(a);
-                    const int32_t p = in.permits;
-                    const int64_t now_ms = floor_div_ms(in.now_ns);
-                    const bool lim_ok = lim < a.n_lim;
-                    if (!lim_ok) lim = 0;
-                    const bool invalid = !lim_ok || op > 2u || (op == 0u && p <= 0);
-                    if (op > 2u) op = 0;
-                    const uint64_t h = mix64(in.key);
-                    rec = Codec::enc(h, now_ms, base, p, op, lim, invalid);
-                    // an invalid request's now is never read: it neither widens the batch's
-                    // time range nor rejects the batch for its span
-                    if (!invalid) {
-                        const int64_t rel = now_ms - base;
-                        // only the compact record keeps now relative to base
-                        if constexpr (std::is_same<Codec, CodecC>::value)
-                            overflow |= rel < 0 || rel > 0xFFFFFFFFLL;
-                        const uint64_t k = ord_key(now_ms);
-                        mn = k < mn ? k : mn;
-                        mx = k > mx ? k : mx;
-                    }
-                    // routing: the upsweep's digit (route-table lookup done once per request)
-                    d = a.digit ? in.dig_v(a)
-                                : ((L.base[lim] + region_local(h, a.shard_bits, L.bits[lim]))
-                                   >> a.digit_shift) & ((1u << a.digit_bits) - 1);
-                } else {
-                    rec = in.rec;
-                    const uint32_t lim = Codec::limiter_of(rec);
-                    d = ((L.base[lim] + region_local(rec.h, a.shard_bits, L.bits[lim]))
-                         >> a.digit_shift) & ((1u << a.digit_bits) - 1);
-                }
-            }
+            Rec rec;
+            uint32_t d;
+            encode_request<Codec>(a, L, base, in, i, n, tr, rec, d);
             const uint32_t abl = a.ablate;
-            const uint64_t m = (abl & kAblNoMatch) ? (1ULL << lane) : wave_match(d, a.digit_bits, active);
-            const uint32_t lr = popc_below(m);
-            const uint32_t cnt = (uint32_t)__popcll(m);
-            const bool leader = active && lr == 0;
-            if (leader) ((uint8_t*)&cntw[d])[wid] = (uint8_t)cnt;
-            if (!(abl & kAblNoBarrier)) __syncthreads();
-            uint32_t pos = 0;
-            if (active) {
-                const uint64_t below = wid == 0 ? 0ULL : cntw[d] & ((1ULL << (8 * wid)) - 1);
-                pos = cur[d] + lr + __builtin_amdgcn_sad_u8((uint32_t)below, 0u, 0u) +
-                      __builtin_amdgcn_sad_u8((uint32_t)(below >> 32), 0u, 0u);
-            }
-            if (!(abl & kAblNoBarrier)) __syncthreads();
-            if (leader) {
-                atomicAdd(&cur[d], cnt);
-                ((uint8_t*)&cntw[d])[wid] = 0;
-            }
+            uint32_t pos = rank_round(cntw, cur, d, a.digit_bits, active, lane, wid,
+                                      abl & kAblNoMatch, abl & kAblNoBarrier);
             if (abl & (kAblNoMatch | kAblNoBarrier)) pos = min(pos, n - 1);
             // inactive lanes write to the padding slot past n (buffers carry spare entries)
             uint32_t wpos = active ? pos : a.n + t;
@@ -286,26 +329,7 @@ __global__ __launch_bounds__(kTileThreads) void k_scatter(PartArgs a) {
             }
         }
     }
-    if constexpr (RAW) {
-        // min / max now over this workgroup's tiles -> one atomic each
-        for (int o = 32; o > 0; o >>= 1) {
-            const uint64_t a1 = __shfl_xor(mn, o, 64), b1 = __shfl_xor(mx, o, 64);
-            mn = a1 < mn ? a1 : mn;
-            mx = b1 > mx ? b1 : mx;
-        }
-        __syncthreads();
-        if (lane == 0) { s_mm[0][wid] = mn; s_mm[1][wid] = mx; }
-        const bool any_over = __syncthreads_or(overflow);
-        if (t == 0) {
-            for (int w = 1; w < kTileThreads / 64; ++w) {
-                mn = s_mm[0][w] < mn ? s_mm[0][w] : mn;
-                mx = s_mm[1][w] > mx ? s_mm[1][w] : mx;
-            }
-            if (mn != ~0ULL) atomicMin((unsigned long long*)&a.ctl->min_now_key, (unsigned long long)mn);
-            if (mx != 0) atomicMax((unsigned long long*)&a.ctl->max_now_key, (unsigned long long)mx);
-            if (any_over) atomicOr(&a.ctl->span_overflow, 1u);
-        }
-    }
+    tr.publish(a.ctl, s_mm);
 }
 
 // ------------------------------------------------------------------ 3b. split scatter
@@ -318,77 +342,45 @@ __global__ __launch_bounds__(kTileThreads) void k_scatter(PartArgs a) {
 // waves (threads 0..kTileThreads-1) read them from LDS, rank, and store — they issue no
 // global load inside a tile, so nothing ever waits behind their stores.
 constexpr int kSplitDepth = 4;       // loader rounds in flight (divides tile_items)
-template <class Codec>
-__host__ __device__ inline size_t split_stage_off(uint32_t bins) {     // in u64 words, 16-B aligned
-    return ((size_t)bins + (bins + 1) / 2 + 1) & ~(size_t)1;
-}
 // ABL (measurement-only instantiations, rl_tune ablate bits 20-25; results wrong): 1 no record
 // store, 2 no position store, 4 records stored at their input index, 8 no ballot match,
 // 16 no encode (the key as the record, digit 0 + lane), 32 whole sectors (each lane its
 // record to both halves of its 32-B sector)
-template <class Codec, bool RAW, int ABL = 0>
+template <class Codec, int ABL = 0>
 __global__ __launch_bounds__(2 * kTileThreads) void k_scatter_split(PartArgs a) {
     using Rec = typename Codec::Rec;
     constexpr int kRecV = (int)(sizeof(Rec) / 16);
     static_assert(sizeof(Rec) % 16 == 0, "records are whole 16-B vectors");
-    extern __shared__ uint64_t dyn_lds64[];
+    extern __shared__ uint64_t dyn_lds64[];           // (scatter_split_lds_bytes)
     __shared__ LimLds L;
     __shared__ uint64_t s_mm[2][2 * kTileThreads / 64];
     const uint32_t t = threadIdx.x, lane = t & 63, wid = t >> 6;
     const bool loader = t >= (uint32_t)kTileThreads;          // (wave-uniform)
     const uint32_t lt = loader ? t - (uint32_t)kTileThreads : t;   // element within a round
-    const uint32_t bins = a.n_bins_pass ? a.n_bins_pass : 1u << a.digit_bits;
+    const uint32_t bins = pass_bins(a);
     uint64_t* cntw = dyn_lds64;                               // as k_scatter
-    uint32_t* cur = (uint32_t*)(dyn_lds64 + bins);
-    Rec* stg = (Rec*)(dyn_lds64 + split_stage_off<Codec>(bins));   // [2][kTileThreads]
-    uint16_t* sdg = (uint16_t*)(stg + 2 * kTileThreads);           // [2][kTileThreads]
-    load_lim_lds(L, a);
-    int64_t base = 0;
-    if constexpr (RAW) base = a.ctl->base_ms;
-    const uint32_t n = a.n_dev ? *a.n_dev : a.n;
+    uint32_t* cur = (uint32_t*)(cntw + bins);
+    Rec* stg = (Rec*)((char*)dyn_lds64 + scatter_stage_off(bins));   // [2][kTileThreads]
+    uint16_t* sdg = (uint16_t*)(stg + 2 * kTileThreads);             // [2][kTileThreads]
+    load_lim_lds(L, a.lims, a.n_lim);
+    const int64_t base = a.ctl->base_ms;
+    const uint32_t n = a.n;
     const uint32_t last = n - 1;
     Rec* out_norm;
     int64_t route_off;
     uint32_t lo_route;
     scatter_outputs(a, out_norm, route_off, lo_route);
-    uint64_t mn = ~0ULL, mx = 0;
-    bool overflow = false;
-    // (loaders) element i's record and digit, as k_scatter's round
-    auto encode = [&](const ScatterIn<Codec, RAW>& in, uint32_t i, Rec& rec, uint32_t& d) __attribute__((always_inline)) {
-        rec = Rec{};
-        d = 0;
-        if (i >= n) return;
-        if constexpr (RAW && (ABL & 16)) {
+    TimeRange tr;
+    // (loaders) element i's record and digit
+    auto encode = [&](const ScatterIn& in, uint32_t i, Rec& rec, uint32_t& d) __attribute__((always_inline)) {
+        if constexpr (ABL & 16) {
+            rec = Rec{};
+            d = 0;
+            if (i >= n) return;
             rec.h = in.key;
             d = (i & 63u) % (a.n_bins_pass ? a.n_bins_pass : 1u);
-            return;
-        }
-        if constexpr (RAW) {
-            uint32_t lim = in.lim_v(a), op = in.op_v(a);
-            const int32_t p = in.permits;
-            const int64_t now_ms = floor_div_ms(in.now_ns);
-            const bool lim_ok = lim < a.n_lim;
-            if (!lim_ok) lim = 0;
-            const bool invalid = !lim_ok || op > 2u || (op == 0u && p <= 0);
-            if (op > 2u) op = 0;
-            const uint64_t h = mix64(in.key);
-            rec = Codec::enc(h, now_ms, base, p, op, lim, invalid);
-            if (!invalid) {
-                const int64_t rel = now_ms - base;
-                if constexpr (std::is_same<Codec, CodecC>::value)
-                    overflow |= rel < 0 || rel > 0xFFFFFFFFLL;
-                const uint64_t k = ord_key(now_ms);
-                mn = k < mn ? k : mn;
-                mx = k > mx ? k : mx;
-            }
-            d = a.digit ? in.dig_v(a)
-                        : ((L.base[lim] + region_local(h, a.shard_bits, L.bits[lim]))
-                           >> a.digit_shift) & ((1u << a.digit_bits) - 1);
         } else {
-            rec = in.rec;
-            const uint32_t lim = Codec::limiter_of(rec);
-            d = ((L.base[lim] + region_local(rec.h, a.shard_bits, L.bits[lim]))
-                 >> a.digit_shift) & ((1u << a.digit_bits) - 1);
+            encode_request<Codec>(a, L, base, in, i, n, tr, rec, d);
         }
     };
     for (uint32_t it = 0;; ++it) {
@@ -403,7 +395,7 @@ __global__ __launch_bounds__(2 * kTileThreads) void k_scatter_split(PartArgs a) 
         // stage round r + 1 from the register ring (slot (r + 1) % depth) and reload that slot
         // with round r + 1 + depth (past the tile: the next tile's inputs, or element n - 1).
         if (loader) {
-            ScatterIn<Codec, RAW> in[kSplitDepth];
+            ScatterIn in[kSplitDepth];
             for (uint32_t b = lt; b < bins; b += kTileThreads)
                 cur[b] = cursor_base(a, b, tile) + a.counts[(size_t)b * a.n_tiles + tile];
 #pragma unroll
@@ -415,7 +407,7 @@ __global__ __launch_bounds__(2 * kTileThreads) void k_scatter_split(PartArgs a) 
             sdg[lt] = (uint16_t)d0;
             in[0].load(a, min(tile0 + (uint32_t)kSplitDepth * kTileThreads + lt, last));
             __syncthreads();
-            auto stage = [&](int r, ScatterIn<Codec, RAW>& nxt) __attribute__((always_inline)) {
+            auto stage = [&](int r, ScatterIn& nxt) __attribute__((always_inline)) {
                 // (the last round stages the next tile's first, unread: that tile's prologue
                 // writes stage 0 again after its first barrier)
                 const uint32_t i = tile0 + (uint32_t)(r + 1) * kTileThreads + lt;
@@ -444,23 +436,8 @@ __global__ __launch_bounds__(2 * kTileThreads) void k_scatter_split(PartArgs a) 
 #pragma unroll
                 for (int k = 0; k < kRecV; ++k) rv[k] = ((const u32x4_t*)stg)[sl * kRecV + k];
                 const uint32_t d = sdg[sl];
-                const uint64_t m = (ABL & 8) ? (active ? 1ULL << lane : 0ULL) : wave_match(d, a.digit_bits, active);
-                const uint32_t lr = popc_below(m);
-                const uint32_t cnt = (uint32_t)__popcll(m);
-                const bool leader = active && lr == 0;
-                if (leader) ((uint8_t*)&cntw[d])[wid] = (uint8_t)cnt;
-                __syncthreads();
-                uint32_t pos = 0;
-                if (active) {
-                    const uint64_t below = wid == 0 ? 0ULL : cntw[d] & ((1ULL << (8 * wid)) - 1);
-                    pos = cur[d] + lr + __builtin_amdgcn_sad_u8((uint32_t)below, 0u, 0u) +
-                          __builtin_amdgcn_sad_u8((uint32_t)(below >> 32), 0u, 0u);
-                }
-                __syncthreads();
-                if (leader) {
-                    atomicAdd(&cur[d], cnt);
-                    ((uint8_t*)&cntw[d])[wid] = 0;
-                }
+                const uint32_t pos = rank_round(cntw, cur, d, a.digit_bits, active, lane, wid,
+                                                (ABL & 8) != 0, false);
                 const uint32_t wpos = (ABL & 4) ? (active ? i : a.n + lt) : active ? min(pos, last) : a.n + lt;
                 Rec* dst = out_norm + ((active && d >= lo_route && !(ABL & 4) ? route_off : 0) + wpos);
                 if constexpr ((ABL & 32) && kRecV == 1) {
@@ -477,369 +454,7 @@ __global__ __launch_bounds__(2 * kTileThreads) void k_scatter_split(PartArgs a) 
             }
         }
     }
-    if constexpr (RAW) {
-        for (int o = 32; o > 0; o >>= 1) {
-            const uint64_t a1 = __shfl_xor(mn, o, 64), b1 = __shfl_xor(mx, o, 64);
-            mn = a1 < mn ? a1 : mn;
-            mx = b1 > mx ? b1 : mx;
-        }
-        __syncthreads();
-        if (lane == 0) { s_mm[0][wid] = mn; s_mm[1][wid] = mx; }
-        const bool any_over = __syncthreads_or(overflow);
-        if (t == 0) {
-            for (int w = 1; w < 2 * kTileThreads / 64; ++w) {
-                mn = s_mm[0][w] < mn ? s_mm[0][w] : mn;
-                mx = s_mm[1][w] > mx ? s_mm[1][w] : mx;
-            }
-            if (mn != ~0ULL) atomicMin((unsigned long long*)&a.ctl->min_now_key, (unsigned long long)mn);
-            if (mx != 0) atomicMax((unsigned long long*)&a.ctl->max_now_key, (unsigned long long)mx);
-            if (any_over) atomicOr(&a.ctl->span_overflow, 1u);
-        }
-    }
-}
-
-// ------------------------------------------------------------------ 3g. local grouping
-// Two-pass batches. Pass 0 partitions by the HIGH dh bits of the region id (bin = region >>
-// s0; routed hot regions to bins of their own), so a normal pass-0 bin holds the records of
-// 2^s0 consecutive regions in arrival order. The bins are then grouped by region inside their
-// own ranges of the final array. A bin is cut into tiles of group_tile_recs records (8192):
-//   k_gtiles  tiles per bin (scan) and each tile's bin;
-//   k_gcount  one wave per tile: its records per region (wave-private LDS counters);
-//   k_gscan   one workgroup per bin: per region, the prefix over the bin's tiles, then the
-//             regions' starts (region-major, then tile: stable) -> each tile's cursors and
-//             the regions' bounds (rstart / rend: the old k_bin_bounds searches are gone);
-//   k_gplace  one wave per tile: rank inside each 64-record round by ballot match, place at
-//             the tile's own cursors (no barrier), pos_out[j] = final position.
-// A tile's output lands in the bin's window (a few hundred KB) within microseconds, so the
-// scattered 16-B record stores complete their sectors while the lines are still in L2 (the
-// global second pass spread every bin's runs over the whole batch and left half-written
-// sectors: write amplification 1.57x). Tiles rather than one workgroup per bin: the largest
-// bins hold ~8x the mean (sw_zipf: 230K records against 30K), and one workgroup per bin made
-// the largest set the stage (2.0 ms). pos_out keeps the unpermute's two gathers local.
-constexpr int kGroupThreads = 256;
-constexpr int kGroupWaves = kGroupThreads / 64;
-constexpr int kGroupDepth = 8;                       // rounds of records in flight per wave
-
-__global__ __launch_bounds__(1024) void k_gtiles(GroupArgs a) {
-    __shared__ uint32_t tmp[16];
-    const uint32_t t = threadIdx.x, nb = a.n_bins0, T = a.tile_recs;
-    const uint32_t per = (nb + 1023) / 1024;
-    const uint32_t b0 = min(t * per, nb), b1 = min(b0 + per, nb);
-    const uint32_t S = a.seg_start ? a.n_segs : 1u;
-    // (segmented: a bin's runs in segment order, tiles never crossing a run)
-    auto run_of = [&](uint32_t b, uint32_t s, uint32_t& st, uint32_t& c) {
-        if (a.seg_start) { st = a.seg_start[b * S + s]; c = a.seg_cnt[b * S + s]; }
-        else { st = a.bin_base[b]; c = a.bin_total[b]; }
-    };
-    uint32_t sum = 0;
-    for (uint32_t b = b0; b < b1; ++b)
-        for (uint32_t s = 0; s < S; ++s) {
-            uint32_t st, c;
-            run_of(b, s, st, c);
-            sum += (c + T - 1) / T;
-        }
-    uint32_t tot;
-    uint32_t base = block_exclusive_scan<1024>(sum, tmp, &tot);
-    for (uint32_t b = b0; b < b1; ++b) {
-        a.tile_base[b] = min(base, a.max_tiles);
-        for (uint32_t s = 0; s < S; ++s) {
-            uint32_t st, c;
-            run_of(b, s, st, c);
-            const uint32_t nt = (c + T - 1) / T;
-            for (uint32_t j = 0; j < nt && base + j < a.max_tiles; ++j) {
-                a.tile_bin[base + j] = b;
-                if (a.seg_start) {
-                    a.tile_beg[base + j] = st + j * T;
-                    a.tile_end[base + j] = st + min((j + 1) * T, c);
-                }
-            }
-            base += nt;
-        }
-    }
-    if (t == 0) a.tile_base[nb] = min(tot, a.max_tiles);
-}
-
-// (tile t of the batch: bin, first record, end)
-__device__ inline void group_tile(const GroupArgs& a, uint32_t t, uint32_t& b, uint32_t& beg,
-                                  uint32_t& end) {
-    b = a.tile_bin[t];
-    if (a.seg_start) {
-        beg = a.tile_beg[t];
-        end = a.tile_end[t];
-        return;
-    }
-    const uint32_t j = t - a.tile_base[b];
-    const uint32_t bb = a.bin_base[b], be = bb + a.bin_total[b];
-    beg = bb + j * a.tile_recs;
-    end = min(beg + a.tile_recs, be);
-}
-
-template <class Codec>
-struct GroupSub {                                    // a record's region inside its bin
-    uint32_t base[256];
-    uint8_t bits[256];
-    __device__ inline void load(const GroupArgs& a) {
-        for (uint32_t l = threadIdx.x; l < a.n_lim; l += blockDim.x) {
-            base[l] = a.lims[l].region_base;
-            bits[l] = (uint8_t)a.lims[l].region_bits;
-        }
-    }
-    __device__ inline uint32_t of(const GroupArgs& a, const typename Codec::Rec& r, uint32_t smask) const {
-        const uint32_t lim = Codec::limiter_of(r);
-        return (base[lim] + region_local(r.h, a.shard_bits, bits[lim])) & smask;
-    }
-};
-
-template <class Codec>
-__global__ __launch_bounds__(kGroupThreads) void k_gcount(GroupArgs a) {
-    using Rec = typename Codec::Rec;
-    extern __shared__ uint32_t gl[];                 // [waves][2^s0]
-    __shared__ GroupSub<Codec> G;
-    G.load(a);
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const uint32_t nsub = 1u << a.sub_bits, smask = nsub - 1u;
-    uint32_t* cw = gl + wid * nsub;
-    const Rec* __restrict__ in = (const Rec*)a.rec_in;
-    const uint32_t n_t = a.tile_base[a.n_bins0];
-    for (uint32_t t = blockIdx.x * kGroupWaves + wid; t < n_t; t += gridDim.x * kGroupWaves) {
-        uint32_t b, beg, end;
-        group_tile(a, t, b, beg, end);
-        for (uint32_t k = lane; k < nsub; k += 64) cw[k] = 0;
-        wave_fence();
-        for (uint32_t i0 = beg; i0 < end; i0 += 64 * kGroupDepth) {
-            Rec r[kGroupDepth];
-#pragma unroll
-            for (int k = 0; k < kGroupDepth; ++k) {
-                const uint32_t i = i0 + (uint32_t)k * 64 + lane;
-                r[k] = ld_rec<kNtRgRec>(in + (i < end ? i : end - 1));
-            }
-#pragma unroll
-            for (int k = 0; k < kGroupDepth; ++k)
-                if (i0 + (uint32_t)k * 64 + lane < end) atomicAdd(&cw[G.of(a, r[k], smask)], 1u);
-        }
-        wave_fence();
-        uint32_t* dst = a.tcount + (size_t)t * nsub;
-        for (uint32_t k = lane; k < nsub; k += 64) dst[k] = cw[k];
-        wave_fence();
-    }
-}
-
-__global__ __launch_bounds__(kGroupThreads) void k_gscan(GroupArgs a) {
-    extern __shared__ uint32_t tot[];                // [2^s0] the regions' record counts
-    __shared__ uint32_t tmp[kGroupWaves];
-    const uint32_t b = blockIdx.x, t = threadIdx.x;
-    const uint32_t nsub = 1u << a.sub_bits;
-    const uint32_t t0 = a.tile_base[b], t1 = a.tile_base[b + 1 <= a.n_bins0 ? b + 1 : b];
-    // per region: the prefix over the bin's tiles (in place)
-    for (uint32_t k = t; k < nsub; k += kGroupThreads) {
-        uint32_t run = 0;
-        for (uint32_t j = t0; j < t1; ++j) {
-            uint32_t* c = a.tcount + (size_t)j * nsub + k;
-            const uint32_t v = *c;
-            *c = run;
-            run += v;
-        }
-        tot[k] = run;
-    }
-    __syncthreads();
-    // the regions' starts: a contiguous chunk of regions per thread, one block scan
-    const uint32_t per = (nsub + kGroupThreads - 1) / kGroupThreads;
-    const uint32_t k0 = min(t * per, nsub), k1 = min(k0 + per, nsub);
-    uint32_t sum = 0;
-    for (uint32_t k = k0; k < k1; ++k) sum += tot[k];
-    uint32_t run = a.bin_base[b] + block_exclusive_scan<kGroupThreads>(sum, tmp, nullptr);
-    const uint32_t g0 = b << a.sub_bits;
-    for (uint32_t k = k0; k < k1; ++k) {
-        const uint32_t c = tot[k];
-        tot[k] = run;
-        if (g0 + k < a.n_regions) {
-            a.rstart[g0 + k] = run;
-            a.rend[g0 + k] = run + c;
-        }
-        run += c;
-    }
-    __syncthreads();
-    for (uint32_t k = t; k < nsub; k += kGroupThreads) {
-        const uint32_t st = tot[k];
-        for (uint32_t j = t0; j < t1; ++j) a.tcount[(size_t)j * nsub + k] += st;
-    }
-}
-
-template <class Codec>
-__global__ __launch_bounds__(kGroupThreads) void k_gplace(GroupArgs a) {
-    using Rec = typename Codec::Rec;
-    extern __shared__ uint32_t gl[];                 // [waves][2^s0]: the tile's cursors
-    __shared__ GroupSub<Codec> G;
-    G.load(a);
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const uint32_t nsub = 1u << a.sub_bits, smask = nsub - 1u;
-    uint32_t* cw = gl + wid * nsub;
-    const Rec* __restrict__ in = (const Rec*)a.rec_in;
-    Rec* __restrict__ out = (Rec*)a.rec_out;
-    const uint32_t n_t = a.tile_base[a.n_bins0];
-    // Every lane loads and stores in every round (past the tile's end: the last record again,
-    // stored to the padding past the batch), and the next rounds' records are loaded before
-    // this round's stores: with no memory operation under a branch the wait-count pass counts
-    // statically, so waiting for a round's records does not drain the stores issued before it
-    // (one vmcnt for both on gfx950).
-    const uint32_t pad = a.pad + lane;
-    for (uint32_t t = blockIdx.x * kGroupWaves + wid; t < n_t; t += gridDim.x * kGroupWaves) {
-        uint32_t b, beg, end;
-        group_tile(a, t, b, beg, end);
-        const uint32_t* src = a.tcount + (size_t)t * nsub;
-        for (uint32_t k = lane; k < nsub; k += 64) cw[k] = src[k];
-        wave_fence();
-        auto load = [&](Rec (&r)[kGroupDepth], uint32_t i0) {
-#pragma unroll
-            for (int k = 0; k < kGroupDepth; ++k) {
-                const uint32_t i = i0 + (uint32_t)k * 64 + lane;
-                r[k] = ld_rec<kNtRgRec>(in + (i < end ? i : end - 1));
-            }
-        };
-        auto place = [&](const Rec (&r)[kGroupDepth], uint32_t i0) {
-#pragma unroll
-            for (int k = 0; k < kGroupDepth; ++k) {
-                const uint32_t i = i0 + (uint32_t)k * 64 + lane;
-                const bool act = i < end;
-                const uint32_t sb = act ? G.of(a, r[k], smask) : 0u;
-                const uint64_t m = wave_match(sb, (int)a.sub_bits, act);
-                const uint32_t lr = popc_below(m);
-                const uint32_t pos = cw[sb] + lr;
-                wave_fence();                            // every lane has read its cursor
-                if (act && lr == 0) cw[sb] = pos + (uint32_t)__popcll(m);
-                wave_fence();
-                const uint32_t wp = (a.ablate & kAblGroupSeq) ? i : pos;
-                st_rec<false>(out + (act ? wp : pad), r[k]);    // (temporal: sectors merge in L2)
-                st<kNtScPos>(a.pos_out + (act ? i : pad), act ? pos : 0u);
-            }
-        };
-        Rec ra[kGroupDepth], rb[kGroupDepth];
-        load(ra, beg);
-        for (uint32_t i0 = beg; i0 < end; i0 += 128 * kGroupDepth) {
-            load(rb, i0 + 64 * kGroupDepth);
-            place(ra, i0);
-            if (i0 + 64 * kGroupDepth >= end) break;     // (wave-uniform)
-            load(ra, i0 + 128 * kGroupDepth);
-            place(rb, i0 + 64 * kGroupDepth);
-        }
-        wave_fence();
-    }
-}
-
-// k_gplace with the tile's records sorted by region in LDS first, in chunks of kGChunk: the
-// global stores then go out as runs of consecutive records per region (a wave-instruction
-// covers a few lines instead of 64 scattered 16-B pieces: with every record scattered,
-// k_gplace ran 1.5 ms on sw_zipf, with the same stores made contiguous 0.9 ms). Each wave
-// ranks its own 256 records of the chunk (4 rounds, ballot match, wave-private counts), the
-// counts are scanned region-major then wave (stable), records go to their sorted slot in
-// LDS, and the chunk is written out in sorted order; the tile's cursors advance per chunk.
-// For bins of up to 2^kGLdsMaxSub regions (wider ones take k_gplace).
-constexpr int kGPThreads = 512;
-constexpr int kGPWaves = kGPThreads / 64;
-constexpr uint32_t kGChunk = 2048;                   // records sorted in LDS at once
-constexpr uint32_t kGLdsMaxSub = 10;
-template <class Rec>
-__host__ __device__ inline size_t gplace_lds_bytes(uint32_t sub_bits) {
-    const size_t nsub = (size_t)1 << sub_bits;
-    return kGChunk * sizeof(Rec) + kGChunk * 2 + kGPWaves * nsub * 2 + 2 * nsub * 4;
-}
-template <class Codec>
-__global__ __launch_bounds__(kGPThreads) void k_gplace_lds(GroupArgs a) {
-    using Rec = typename Codec::Rec;
-    extern __shared__ uint4 glds[];
-    __shared__ GroupSub<Codec> G;
-    __shared__ uint32_t s_tmp[kGPWaves];
-    const uint32_t t = threadIdx.x, lane = t & 63, wid = t >> 6;
-    const uint32_t nsub = 1u << a.sub_bits, smask = nsub - 1u;
-    Rec* stg = (Rec*)glds;                            // [kGChunk] the chunk, sorted
-    uint16_t* ssub = (uint16_t*)(stg + kGChunk);      // [kGChunk] their regions
-    uint16_t* hist = ssub + kGChunk;                  // [waves][nsub] counts, then wave prefixes
-    uint32_t* tsub = (uint32_t*)(hist + kGPWaves * nsub);   // [nsub] chunk-local region starts
-    uint32_t* gcur = tsub + nsub;                     // [nsub] the tile's global cursors
-    G.load(a);
-    const Rec* __restrict__ in = (const Rec*)a.rec_in;
-    Rec* __restrict__ out = (Rec*)a.rec_out;
-    const uint32_t n_t = a.tile_base[a.n_bins0];
-    const uint32_t per = (nsub + kGPThreads - 1) / kGPThreads;
-    const uint32_t k0 = min(t * per, nsub), k1 = min(k0 + per, nsub);
-    for (uint32_t tt = blockIdx.x; tt < n_t; tt += gridDim.x) {
-        uint32_t b, beg, end;
-        group_tile(a, tt, b, beg, end);
-        __syncthreads();                              // the previous tile's readers are done
-        for (uint32_t k = t; k < nsub; k += kGPThreads) gcur[k] = a.tcount[(size_t)tt * nsub + k];
-        for (uint32_t c0 = beg; c0 < end; c0 += kGChunk) {
-            const uint32_t c1 = min(c0 + kGChunk, end);
-            for (uint32_t k = t; k < kGPWaves * nsub; k += kGPThreads) hist[k] = 0;
-            // this wave's 256 records of the chunk: 4 rounds, loaded together
-            const uint32_t w0 = c0 + wid * 256u;
-            Rec r[4];
-            uint32_t sb[4], wr[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const uint32_t j = w0 + (uint32_t)q * 64 + lane;
-                r[q] = ld_rec<kNtRgRec>(in + (j < c1 ? j : c1 - 1));
-            }
-            __syncthreads();                          // hist zeroed (and gcur loaded)
-            uint16_t* hw = hist + wid * nsub;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const uint32_t j = w0 + (uint32_t)q * 64 + lane;
-                const bool act = j < c1;
-                sb[q] = act ? G.of(a, r[q], smask) : 0u;
-                const uint64_t m = wave_match(sb[q], (int)a.sub_bits, act);
-                const uint32_t lr = popc_below(m);
-                wr[q] = (uint32_t)hw[sb[q]] + lr;    // rank among this wave's records of the region
-                wave_fence();
-                if (act && lr == 0) hw[sb[q]] = (uint16_t)(wr[q] + (uint32_t)__popcll(m));
-                wave_fence();
-            }
-            __syncthreads();
-            // region-major, then wave: each region's start in the chunk, each wave's offset in it
-            uint32_t sum = 0;
-            for (uint32_t k = k0; k < k1; ++k) {
-                uint32_t run = 0;
-                for (uint32_t w = 0; w < (uint32_t)kGPWaves; ++w) {
-                    const uint32_t v = hist[w * nsub + k];
-                    hist[w * nsub + k] = (uint16_t)run;
-                    run += v;
-                }
-                tsub[k] = run;                        // (the region's count, for now)
-                sum += run;
-            }
-            uint32_t base = block_exclusive_scan<kGPThreads>(sum, s_tmp, nullptr);
-            for (uint32_t k = k0; k < k1; ++k) {
-                const uint32_t c = tsub[k];
-                tsub[k] = base;
-                base += c;
-            }
-            __syncthreads();
-            // sorted slots in LDS; the final position of every pass-0 position
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const uint32_t j = w0 + (uint32_t)q * 64 + lane;
-                if (j < c1) {
-                    const uint32_t o = (uint32_t)hist[wid * nsub + sb[q]] + wr[q];
-                    stg[tsub[sb[q]] + o] = r[q];
-                    ssub[tsub[sb[q]] + o] = (uint16_t)sb[q];
-                    st<kNtScPos>(a.pos_out + j, gcur[sb[q]] + o);
-                }
-            }
-            __syncthreads();
-            // the chunk in sorted order: runs of consecutive records per region
-            for (uint32_t i = t; i < c1 - c0; i += kGPThreads) {
-                const uint32_t k = ssub[i];
-                st_rec<false>(out + gcur[k] + (i - tsub[k]), stg[i]);
-            }
-            __syncthreads();
-            // the tile's cursors past this chunk
-            for (uint32_t k = k0; k < k1; ++k) {
-                const uint32_t nx = k + 1 < nsub ? tsub[k + 1] : c1 - c0;
-                gcur[k] += nx - tsub[k];
-            }
-        }
-    }
+    tr.publish(a.ctl, s_mm);
 }
 
 // ------------------------------------------------------------------ segmented pass 0
@@ -885,20 +500,9 @@ __global__ __launch_bounds__(1024) void k_seg_base(const uint32_t* __restrict__ 
         }
 }
 
-hipError_t launch_seg_base(const uint32_t* counts, const uint32_t* bin_total,
-                           const uint32_t* bin_base, uint32_t bins, uint32_t lo_bins,
-                           uint32_t n_tiles, uint32_t seg_tiles, uint32_t n_segs,
-                           uint32_t* seg_adj, uint32_t* seg_start, uint32_t* seg_cnt, hipStream_t s) {
-    if (seg_tiles == 0 || (size_t)(n_segs - 1) * seg_tiles >= n_tiles || lo_bins > bins)
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_seg_base, dim3(1), dim3(1024), 0, s, counts, bin_total, bin_base, bins,
-                       lo_bins, n_tiles, seg_tiles, n_segs, seg_adj, seg_start, seg_cnt);
-    return hipGetLastError();
-}
-
 // ------------------------------------------------------------------ routing helpers
-// After the pass-0 scan: the routed bins' ranges (pass 1 reuses bin_base / bin_total) and
-// the number of normal records, which pass 1 and the unpermute read on device.
+// After the pass-0 scan: the routed bins' ranges and the number of normal records, which the
+// grouping, the region stage and the unpermute read on device.
 __global__ __launch_bounds__(1024) void k_route_ranges(const uint32_t* __restrict__ route_list,
                                                        const uint32_t* __restrict__ bin_base,
                                                        const uint32_t* __restrict__ bin_total,
@@ -913,288 +517,47 @@ __global__ __launch_bounds__(1024) void k_route_ranges(const uint32_t* __restric
     if (threadIdx.x == 0) ctl->n_normal = bin_base[lo_bins];
 }
 
-// ------------------------------------------------------------------ 5. unpermute
-template <class Res>
-__global__ __launch_bounds__(kTileThreads) void k_unpermute(UnpermArgs a) {
-  const uint32_t t = threadIdx.x;
-  const Res* __restrict__ res = (const Res*)a.res;
-  const uint32_t* __restrict__ pos0 = a.pos0;
-  const uint32_t* __restrict__ pos1 = a.pos1;
-  uint8_t* __restrict__ allowed = a.allowed;
-  int64_t* __restrict__ remaining = a.remaining;
-  constexpr int B = 8;                         // rounds per batch (loads issued together)
-  constexpr int NB = kTileItems / B;
-  const bool simple = pos1 || a.tokens_out || (a.ablate & kAblNoGather);
-  // two-pass batches: mid (res) holds the normal records' results in pass-0 order, res_hi
-  // the routed records' results at their own (pass-0) positions >= n_normal
-  const Res* __restrict__ res_hi = (const Res*)a.res_hi;
-  const uint32_t nn = res_hi ? a.ctl->n_normal : 0u;
-  for (uint32_t it = 0;; ++it) {
-    const uint32_t tile = tile_at(it, a.n_tiles);
-    if (tile >= a.n_tiles) break;
-    const uint32_t tbase = tile * (uint32_t)kTile + t;
-    if (!simple && tile * (uint64_t)kTile + kTile <= a.n) {
-        // Full tile, one result array: software-pipelined so that every wait is for loads
-        // issued a batch earlier and never directly behind the previous batch's stores
-        // (vmcnt retires loads and stores in issue order).
-        uint32_t pE[B], pO[B];
-        Res vE[B], vO[B];
-        auto load = [&](uint32_t (&p)[B], int b) {
-#pragma unroll
-            for (int k = 0; k < B; ++k) p[k] = ld<kNtUn>(pos0 + tbase + (uint32_t)(b * B + k) * kTileThreads);
-        };
-        auto gather = [&](Res (&v)[B], const uint32_t (&p)[B]) {
-#pragma unroll
-            for (int k = 0; k < B; ++k) v[k] = (res_hi && p[k] >= nn ? res_hi : res)[p[k]];
-        };
-        auto store = [&](const Res (&v)[B], int b) {
-#pragma unroll
-            for (int k = 0; k < B; ++k) {
-                const uint32_t i = tbase + (uint32_t)(b * B + k) * kTileThreads;
-                st<kNtUn>(allowed + i, (uint8_t)(v[k] & 1u));
-                st<kNtUn>(remaining + i, (int64_t)(v[k] >> 1) - kResBias);
-            }
-        };
-        load(pE, 0);
-        for (int b = 0; b < NB; b += 2) {
-            gather(vE, pE);
-            load(pO, b + 1);
-            if (b > 0) store(vO, b - 1);
-            gather(vO, pO);
-            load(pE, (b + 2) % NB);                 // unconditional (last one unused)
-            store(vE, b);
-        }
-        store(vO, NB - 1);
-        continue;
-    }
-    for (int r0 = 0; r0 < kTileItems; r0 += B) {
-        uint32_t p[B];
-        Res v[B];
-#pragma unroll
-        for (int k = 0; k < B; ++k) {
-            const uint32_t i = tile * (uint32_t)kTile + (uint32_t)(r0 + k) * kTileThreads + t;
-            p[k] = pos0[i < a.n ? i : 0];
-        }
-        if (pos1) {
-            // pass 1 moved the normal records only; routed ones kept their pass-0 position
-            const uint32_t nn = a.ctl->n_normal;
-#pragma unroll
-            for (int k = 0; k < B; ++k) p[k] = p[k] < nn ? pos1[p[k]] : p[k];
-        }
-        if (a.ablate & kAblNoGather) {
-#pragma unroll
-            for (int k = 0; k < B; ++k) v[k] = (Res)p[k];
-        } else {
-#pragma unroll
-            for (int k = 0; k < B; ++k) v[k] = (res_hi && p[k] >= nn ? res_hi : res)[p[k]];
-        }
-#pragma unroll
-        for (int k = 0; k < B; ++k) {
-            const uint32_t i = tile * (uint32_t)kTile + (uint32_t)(r0 + k) * kTileThreads + t;
-            if (i < a.n) {
-                allowed[i] = (uint8_t)(v[k] & 1u);
-                remaining[i] = (int64_t)(v[k] >> 1) - kResBias;
-                if (a.tokens_out) a.tokens_out[i] = a.tok ? a.tok[p[k]] : __builtin_nan("");
-            }
-        }
-    }
-  }
-  if (a.ctl && a.ctl->n_esc != 0) {
-    // Rare (TB balances below -3 after time regression): the gather above decoded the
-    // escape code as (allowed 1, remaining -3); rewrite those results from the side array.
-    // Same tiles, same thread per element as above, so the rewrite follows the first store.
-    const Res* rf = (const Res*)a.res_final;
-    for (uint32_t it = 0;; ++it) {
-      const uint32_t tile = tile_at(it, a.n_tiles);
-      if (tile >= a.n_tiles) break;
-      for (int r = 0; r < kTileItems; ++r) {
-        const uint32_t i = tile * (uint32_t)kTile + (uint32_t)r * kTileThreads + t;
-        if (i >= a.n) break;
-        uint32_t j = pos0[i];
-        if (a.pos1_final && j < a.ctl->n_normal) j = a.pos1_final[j];
-        if ((uint64_t)rf[j] == kResEscape) {
-          allowed[i] = 0;
-          remaining[i] = a.ext[j];
-        }
-      }
-    }
-  }
-}
-
-// Split unpermute (rl_tune unpermute_split): the position reads and result gathers in loader
-// waves (threads kTileThreads..), the decision stores in storer waves, one round apart through
-// LDS, so that no wait for a gather sits behind the acks of earlier stores (one vmcnt for both
-// on gfx950). Loaders keep kUnPosDepth rounds of positions and kUnGatherDepth rounds of
-// gathers in flight. One-array batches only (no pos1 pass, no tokens): k_unpermute otherwise.
-constexpr int kUnPosDepth = 8, kUnGatherDepth = 4;
-template <class Res>
-__global__ __launch_bounds__(2 * kTileThreads) void k_unpermute_split(UnpermArgs a) {
-    __shared__ Res stage[2][kTileThreads];
-    const uint32_t t = threadIdx.x;
-    const bool loader = t >= (uint32_t)kTileThreads;          // (wave-uniform)
-    const uint32_t lt = loader ? t - (uint32_t)kTileThreads : t;
-    const Res* __restrict__ res = (const Res*)a.res;
-    const Res* __restrict__ res_hi = (const Res*)a.res_hi;
-    const uint32_t nn = res_hi ? a.ctl->n_normal : 0u;
-    const uint32_t last = a.n - 1;
-    for (uint32_t it = 0;; ++it) {
-        const uint32_t tile = tile_at(it, a.n_tiles);
-        if (tile >= a.n_tiles) break;
-        const uint32_t tbase = tile * (uint32_t)kTile + lt;
-        __syncthreads();                                      // last tile's stage readers are done
-        if (loader) {
-            uint32_t P[kUnPosDepth];
-            Res V[kUnGatherDepth];
-            auto pos_of = [&](int r) { return ld<kNtUn>(a.pos0 + min(tbase + (uint32_t)r * kTileThreads, last)); };
-            auto gather = [&](uint32_t p) { return (res_hi && p >= nn ? res_hi : res)[p]; };
-#pragma unroll
-            for (int k = 0; k < kUnPosDepth; ++k) P[k] = pos_of(k);
-#pragma unroll
-            for (int k = 0; k < kUnGatherDepth; ++k) {
-                V[k] = gather(P[k]);
-                P[k] = pos_of(k + kUnPosDepth);
-            }
-            // round r: stage round r's results; gather round r + G (its position, slot
-            // (r + G) % D, arrived); reload that slot with round r + G + D
-            for (int r0 = 0; r0 < kTileItems; r0 += kUnPosDepth) {
-#pragma unroll
-                for (int k = 0; k < kUnPosDepth; ++k) {
-                    const int r = r0 + k;
-                    stage[r & 1][lt] = V[k % kUnGatherDepth];
-                    V[k % kUnGatherDepth] = gather(P[(k + kUnGatherDepth) % kUnPosDepth]);
-                    P[(k + kUnGatherDepth) % kUnPosDepth] = pos_of(r + kUnGatherDepth + kUnPosDepth);
-                    __syncthreads();
-                }
-            }
-        } else {
-            for (int r = 0; r < kTileItems; ++r) {
-                __syncthreads();
-                const Res v = stage[r & 1][lt];
-                const uint32_t i = tbase + (uint32_t)r * kTileThreads;
-                if (i < a.n) {
-                    st<kNtUn>(a.allowed + i, (uint8_t)(v & 1u));
-                    st<kNtUn>(a.remaining + i, (int64_t)(v >> 1) - kResBias);
-                }
-            }
-        }
-    }
-    if (!loader && a.ctl && a.ctl->n_esc != 0) {
-        // as k_unpermute: the escape code decoded as (allowed 1, remaining -3) is rewritten
-        // from the side array by the thread that stored it
-        const Res* rf = (const Res*)a.res_final;
-        for (uint32_t it = 0;; ++it) {
-            const uint32_t tile = tile_at(it, a.n_tiles);
-            if (tile >= a.n_tiles) break;
-            for (int r = 0; r < kTileItems; ++r) {
-                const uint32_t i = tile * (uint32_t)kTile + (uint32_t)r * kTileThreads + t;
-                if (i >= a.n) break;
-                uint32_t j = a.pos0[i];
-                if (a.pos1_final && j < a.ctl->n_normal) j = a.pos1_final[j];
-                if ((uint64_t)rf[j] == kResEscape) {
-                    a.allowed[i] = 0;
-                    a.remaining[i] = a.ext[j];
-                }
-            }
-        }
-    }
-}
-
-// Two-pass batches: undo the high-digit pass first. mid[j] = res[pos1[j]] for j in
-// pass-0 order: pos1 is read in order and, since pass 0 left the records sorted by low
-// digit, consecutive j fall into one low-digit run whose elements go to the 2^d1
-// high-digit bins in order — the gather walks 2^d1 sequential streams instead of the
-// whole result array. k_unpermute then gathers mid[pos0[i]] (2^d0 streams). Two
-// local gathers replace the composed res[pos1[pos0[i]]], which hit a random line of a
-// 1 GB index and of the result array per request.
-// Routed records (pass-0 positions >= ctl->n_normal) skipped pass 1: k_unpermute reads
-// their results in place (UnpermArgs::res_hi), so mid covers the normal records only.
-template <class Res>
-__global__ __launch_bounds__(256) void k_unpermute_mid(const uint32_t* __restrict__ pos1,
-                                                       const Res* __restrict__ res,
-                                                       Res* __restrict__ mid, uint32_t n,
-                                                       const BatchCtl* __restrict__ ctl, uint32_t xcd) {
-    constexpr int B = 8;
-    // consecutive blocks of j on one XCD: a pass-0 bin's 2^d1 result streams are then read
-    // through one L2 instead of being fetched into all eight
-    const uint32_t base = (xcd ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x) * (256u * B) + threadIdx.x;
-    n = min(n, ctl->n_normal);
-    if (base >= n) return;
-    uint32_t p[B];
-#pragma unroll
-    for (int k = 0; k < B; ++k) {
-        const uint32_t j = base + (uint32_t)k * 256u;
-        p[k] = pos1[j < n ? j : base];
-    }
-    Res v[B];
-#pragma unroll
-    for (int k = 0; k < B; ++k) v[k] = res[p[k]];
-#pragma unroll
-    for (int k = 0; k < B; ++k) {
-        const uint32_t j = base + (uint32_t)k * 256u;
-        if (j < n) mid[j] = v[k];
-    }
-}
-
-__global__ void k_fill_invalid(uint8_t* allowed, int64_t* remaining, double* tok, uint32_t n) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        allowed[i] = 0;
-        remaining[i] = kRemInvalid;
-        if (tok) tok[i] = __builtin_nan("");
-    }
-}
-
-
-hipError_t launch_upsweep(const PartArgs& a, bool raw, bool wide, hipStream_t s) {
+// ------------------------------------------------------------------ launchers
+hipError_t launch_upsweep(const PartArgs& a, hipStream_t s) {
     dim3 grid(persistent_grid(a.n_tiles, a.up_per_cu ? a.up_per_cu : 4)), block(kTileThreads);
-    const uint32_t bins = a.n_bins_pass ? a.n_bins_pass : 1u << a.digit_bits;
+    const uint32_t bins = pass_bins(a);
     if (bins > (1u << kMaxDigitBits)) return hipErrorInvalidValue;
-    const size_t lds = bins * sizeof(uint32_t) + (a.route_list ? sizeof(RouteLds) : 0);
-    if (raw && a.digit) {
-        if (wide) hipLaunchKernelGGL((k_upsweep<CodecW, true, true>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((k_upsweep<CodecC, true, true>), grid, block, lds, s, a);
-    } else if (raw) {
-        if (wide) hipLaunchKernelGGL((k_upsweep<CodecW, true, false>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((k_upsweep<CodecC, true, false>), grid, block, lds, s, a);
-    } else {
-        return hipErrorInvalidValue;         // (record-input passes: k_group since round 6)
-    }
+    const size_t lds = upsweep_lds_bytes(bins, a.route_list != nullptr);
+    if (a.digit) hipLaunchKernelGGL(k_upsweep<true>, grid, block, lds, s, a);
+    else hipLaunchKernelGGL(k_upsweep<false>, grid, block, lds, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_scatter(const PartArgs& a, bool raw, bool wide, hipStream_t s) {
+template <int ABL>
+static void scatter_split_abl(const PartArgs& a, dim3 grid, size_t lds, hipStream_t s) {
+    hipLaunchKernelGGL((k_scatter_split<CodecC, ABL>), grid, dim3(2 * kTileThreads), lds, s, a);
+}
+
+hipError_t launch_scatter(const PartArgs& a, bool wide, hipStream_t s) {
     dim3 grid(persistent_grid(a.n_tiles, a.sc_per_cu ? a.sc_per_cu : 1)), block(kTileThreads);
-    const uint32_t bins = a.n_bins_pass ? a.n_bins_pass : 1u << a.digit_bits;
+    const uint32_t bins = pass_bins(a);
     if (bins > (1u << kMaxDigitBits)) return hipErrorInvalidValue;
-    if (a.sc_split && (a.ablate >> 20) && raw && !wide) {   // measurement-only variants
-        const dim3 b2(2 * kTileThreads);
-        const size_t lc = split_stage_off<CodecC>(bins) * 8 + 2 * kTileThreads * (sizeof(RecC) + 2);
+    const dim3 b2(2 * kTileThreads);
+    const size_t lc = scatter_split_lds_bytes<CodecC>(bins), lw = scatter_split_lds_bytes<CodecW>(bins);
+    if (a.sc_split && (a.ablate >> 20) && !wide) {   // measurement-only variants
         switch ((a.ablate >> 20) & 63u) {
-            case 1: hipLaunchKernelGGL((k_scatter_split<CodecC, true, 1>), grid, b2, lc, s, a); break;
-            case 2: hipLaunchKernelGGL((k_scatter_split<CodecC, true, 2>), grid, b2, lc, s, a); break;
-            case 3: hipLaunchKernelGGL((k_scatter_split<CodecC, true, 3>), grid, b2, lc, s, a); break;
-            case 4: hipLaunchKernelGGL((k_scatter_split<CodecC, true, 4>), grid, b2, lc, s, a); break;
-            case 8: hipLaunchKernelGGL((k_scatter_split<CodecC, true, 8>), grid, b2, lc, s, a); break;
-            case 16: hipLaunchKernelGGL((k_scatter_split<CodecC, true, 16>), grid, b2, lc, s, a); break;
-            case 27: hipLaunchKernelGGL((k_scatter_split<CodecC, true, 27>), grid, b2, lc, s, a); break;
-            case 32: hipLaunchKernelGGL((k_scatter_split<CodecC, true, 32>), grid, b2, lc, s, a); break;
+            case 1: scatter_split_abl<1>(a, grid, lc, s); break;
+            case 2: scatter_split_abl<2>(a, grid, lc, s); break;
+            case 3: scatter_split_abl<3>(a, grid, lc, s); break;
+            case 4: scatter_split_abl<4>(a, grid, lc, s); break;
+            case 8: scatter_split_abl<8>(a, grid, lc, s); break;
+            case 16: scatter_split_abl<16>(a, grid, lc, s); break;
+            case 27: scatter_split_abl<27>(a, grid, lc, s); break;
+            case 32: scatter_split_abl<32>(a, grid, lc, s); break;
             default: return hipErrorInvalidValue;
         }
-        return hipGetLastError();
+    } else if (a.sc_split && !a.ablate) {
+        if (wide) hipLaunchKernelGGL((k_scatter_split<CodecW>), grid, b2, lw, s, a);
+        else hipLaunchKernelGGL((k_scatter_split<CodecC>), grid, b2, lc, s, a);
+    } else {
+        if (wide) hipLaunchKernelGGL((k_scatter<CodecW>), grid, block, scatter_lds_bytes(bins), s, a);
+        else hipLaunchKernelGGL((k_scatter<CodecC>), grid, block, scatter_lds_bytes(bins), s, a);
     }
-    if (a.sc_split && !a.ablate) {
-        const dim3 b2(2 * kTileThreads);
-        const size_t lc = split_stage_off<CodecC>(bins) * 8 + 2 * kTileThreads * (sizeof(RecC) + 2);
-        const size_t lw = split_stage_off<CodecW>(bins) * 8 + 2 * kTileThreads * (sizeof(RecW) + 2);
-        if (!raw) return hipErrorInvalidValue;   // (record-input passes: k_group since round 6)
-        if (wide) hipLaunchKernelGGL((k_scatter_split<CodecW, true>), grid, b2, lw, s, a);
-        else hipLaunchKernelGGL((k_scatter_split<CodecC, true>), grid, b2, lc, s, a);
-        return hipGetLastError();
-    }
-    const size_t lds = bins * (sizeof(uint64_t) + sizeof(uint32_t));
-    if (!raw) return hipErrorInvalidValue;
-    if (wide) hipLaunchKernelGGL((k_scatter<CodecW, true>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((k_scatter<CodecC, true>), grid, block, lds, s, a);
     return hipGetLastError();
 }
 
@@ -1209,70 +572,15 @@ hipError_t launch_scan_small(const uint32_t* in, uint32_t* out, uint32_t len, hi
     return hipGetLastError();
 }
 
-hipError_t launch_add_rows(const uint32_t* row_base, uint32_t* data, uint32_t rows,
-                           uint32_t cols, hipStream_t s) {
-    hipLaunchKernelGGL(k_add_rows, dim3(rows), dim3(256), 0, s, row_base, data, cols);
-    return hipGetLastError();
-}
-
-// Fold the sharded batch counters into BatchCtl and clear them for the next batch.
-__global__ __launch_bounds__(256) void k_stats_reduce(unsigned long long* stats, BatchCtl* ctl) {
-    __shared__ unsigned long long part[kStWords][4];
-    const uint32_t t = threadIdx.x, lane = t & 63, wid = t >> 6;
-    unsigned long long acc[kStCount] = {};
-    for (uint32_t s = t; s < kStatSlots; s += 256) {
-        unsigned long long* p = stats + (size_t)s * kStWords;
-#pragma unroll
-        for (int k = 0; k < (int)kStCount; ++k) { acc[k] += p[k]; p[k] = 0; }
-    }
-#pragma unroll
-    for (int k = 0; k < (int)kStCount; ++k) {
-        unsigned long long v = acc[k];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) part[k][wid] = v;
-    }
-    __syncthreads();
-    if (t < kStCount) {
-        const unsigned long long v = part[t][0] + part[t][1] + part[t][2] + part[t][3];
-        unsigned long long* dst = t == kStAllowed ? &ctl->allowed : t == kStInvalid ? &ctl->invalid
-                                : t == kStCapErr ? &ctl->cap_err : t == kStDistinct ? &ctl->distinct
-                                : t == kStRegions ? &ctl->regions : t == kStCacheHits ? &ctl->cache_hits
-                                : &ctl->table_bytes;
-        *dst += v;
-    }
-}
-
-hipError_t launch_stats_reduce(unsigned long long* stats, BatchCtl* ctl, hipStream_t s) {
-    hipLaunchKernelGGL(k_stats_reduce, dim3(1), dim3(256), 0, s, stats, ctl);
-    return hipGetLastError();
-}
-
-hipError_t launch_group(const GroupArgs& a, bool wide, hipStream_t s) {
-    if (a.n_bins0 == 0 || a.sub_bits > (uint32_t)kMaxDigitBits || a.max_tiles == 0)
+hipError_t launch_seg_base(const uint32_t* counts, const uint32_t* bin_total,
+                           const uint32_t* bin_base, uint32_t bins, uint32_t lo_bins,
+                           uint32_t n_tiles, uint32_t seg_tiles, uint32_t n_segs,
+                           uint32_t* seg_adj, uint32_t* seg_start, uint32_t* seg_cnt, hipStream_t s) {
+    if (seg_tiles == 0 || (size_t)(n_segs - 1) * seg_tiles >= n_tiles || lo_bins > bins)
         return hipErrorInvalidValue;
-    const size_t nsub = (size_t)1 << a.sub_bits;
-    const size_t lds = kGroupWaves * nsub * sizeof(uint32_t);
-    // one wave per tile: a persistent grid over the (device-counted) tiles
-    const dim3 gw(persistent_grid((a.max_tiles + kGroupWaves - 1) / kGroupWaves, 8)), b(kGroupThreads);
-    hipLaunchKernelGGL(k_gtiles, dim3(1), dim3(1024), 0, s, a);
-    if (wide) hipLaunchKernelGGL(k_gcount<CodecW>, gw, b, lds, s, a);
-    else hipLaunchKernelGGL(k_gcount<CodecC>, gw, b, lds, s, a);
-    hipLaunchKernelGGL(k_gscan, dim3(a.n_bins0), b, nsub * sizeof(uint32_t), s, a);
-    if (a.sub_bits <= kGLdsMaxSub && !(a.ablate & kAblGroupSeq)) {
-        const dim3 gp(persistent_grid((a.max_tiles + 1) / 2, 4)), bp(kGPThreads);
-        if (wide) hipLaunchKernelGGL(k_gplace_lds<CodecW>, gp, bp, gplace_lds_bytes<RecW>(a.sub_bits), s, a);
-        else hipLaunchKernelGGL(k_gplace_lds<CodecC>, gp, bp, gplace_lds_bytes<RecC>(a.sub_bits), s, a);
-        return hipGetLastError();
-    }
-    if (wide) hipLaunchKernelGGL(k_gplace<CodecW>, gw, b, lds, s, a);
-    else hipLaunchKernelGGL(k_gplace<CodecC>, gw, b, lds, s, a);
+    hipLaunchKernelGGL(k_seg_base, dim3(1), dim3(1024), 0, s, counts, bin_total, bin_base, bins,
+                       lo_bins, n_tiles, seg_tiles, n_segs, seg_adj, seg_start, seg_cnt);
     return hipGetLastError();
-}
-
-template <class Res>
-static void unpermute_mid(const UnpermArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_unpermute_mid<Res>, dim3((a.n + 2047) / 2048), dim3(256), 0, s, a.pos1,
-                       (const Res*)a.res, (Res*)a.mid, a.n, a.ctl, a.mid_xcd);
 }
 
 hipError_t launch_route_ranges(const uint32_t* route_list, const uint32_t* bin_base,
@@ -1280,42 +588,6 @@ hipError_t launch_route_ranges(const uint32_t* route_list, const uint32_t* bin_b
                                uint32_t* route_cnt, BatchCtl* ctl, hipStream_t s) {
     hipLaunchKernelGGL(k_route_ranges, dim3(1), dim3(1024), 0, s, route_list, bin_base, bin_total,
                        lo_bins, route_start, route_cnt, ctl);
-    return hipGetLastError();
-}
-
-hipError_t launch_unpermute(const UnpermArgs& a_in, int res_bytes, hipStream_t s) {
-    UnpermArgs a = a_in;
-    a.res_final = a.res;
-    a.pos1_final = a.pos1;
-    if (a.pos1 && a.mid && !a.tokens_out && a.n) {      // two-pass: undo pass 1, then pass 0
-        if (res_bytes == 8) unpermute_mid<uint64_t>(a, s);
-        else if (res_bytes == 1) unpermute_mid<uint8_t>(a, s);
-        else if (res_bytes == 2) unpermute_mid<uint16_t>(a, s);
-        else unpermute_mid<uint32_t>(a, s);
-        a.res_hi = a.res;
-        a.res = a.mid;
-        a.pos1 = nullptr;
-    }
-    dim3 g(persistent_grid(a.n_tiles, a.per_cu ? a.per_cu : 1)), b(kTileThreads);
-    if (a.split && !a.pos1 && !a.tokens_out && !a.ablate) {
-        const dim3 b2(2 * kTileThreads);
-        if (res_bytes == 8) hipLaunchKernelGGL(k_unpermute_split<uint64_t>, g, b2, 0, s, a);
-        else if (res_bytes == 1) hipLaunchKernelGGL(k_unpermute_split<uint8_t>, g, b2, 0, s, a);
-        else if (res_bytes == 2) hipLaunchKernelGGL(k_unpermute_split<uint16_t>, g, b2, 0, s, a);
-        else hipLaunchKernelGGL(k_unpermute_split<uint32_t>, g, b2, 0, s, a);
-        return hipGetLastError();
-    }
-    if (res_bytes == 8) hipLaunchKernelGGL(k_unpermute<uint64_t>, g, b, 0, s, a);
-    else if (res_bytes == 1) hipLaunchKernelGGL(k_unpermute<uint8_t>, g, b, 0, s, a);
-    else if (res_bytes == 2) hipLaunchKernelGGL(k_unpermute<uint16_t>, g, b, 0, s, a);
-    else hipLaunchKernelGGL(k_unpermute<uint32_t>, g, b, 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_fill_invalid(uint8_t* allowed, int64_t* remaining, double* tok, uint32_t n,
-                               hipStream_t s) {
-    hipLaunchKernelGGL(k_fill_invalid, dim3((n + 255) / 256), dim3(256), 0, s, allowed,
-                       remaining, tok, n);
     return hipGetLastError();
 }
 
