@@ -92,19 +92,31 @@ struct Slot {
     uint64_t a, b, c;
 };
 
-// HBM slot invariant (open addressing, linear probing from a key's 4-aligned home):
-// a slot is FREE iff its four words (and its local-cache word) are all zero; a key is
-// always found before the first free slot of its probe sequence. A slot whose state is
-// dead (no bucket live) but whose words are not all zero is a TOMBSTONE: it keeps the
-// probe chain intact and may be reused by an insert. The TTL sweep rewrites whole regions: it
-// drops dead slots (written as zeros) and rebuilds the chains; state import and table growth
-// rebuild them too and drop the slots that hold no state at all. A batch's region loaded as an LDS image keeps its dead slots as tombstones where
-// they are, and only once live + dead slots crowd the region (> kTombCrowd, rl_region.hpp)
-// drops them and relinks; sparse region waves (few records) touch single buckets and never
-// create a hole. So used slots = live keys + tombstones (rl_usage.used_slots), and only a
-// sweep brings the two together. The only key whose dead state could be all-zero (tag 0 =
-// mix64(0) with a deleted token bucket) is written with c = kDeadMark instead, which no live
-// state has (TB: c bit 0 clear = absent bucket; SW: both counts zero).
+// HBM slot invariant (open addressing, linear probing from a key's 4-aligned home, wrapping
+// inside the key's region). Every kernel that reads or writes a table relies on it, and
+// rl_check_limiter (rl_check.hpp, rl_check.hip) verifies it:
+//  * A slot is FREE iff its four words and its local-cache word are all zero.
+//  * A key sits before the first free slot of its probe sequence: a lookup stops at that slot
+//    and reports the key absent (quad_resolve, rl_table.hpp), so no writer may leave a hole
+//    in a chain.
+//  * A slot whose state is dead (reset, or no bucket live) but whose words are not all zero is
+//    a TOMBSTONE: it stays where it is, keeps the chain intact, never hits, and an insert may
+//    claim it. So used slots = live keys + tombstones (rl_usage.used_slots).
+//  * A used slot is never all-zero: the one key whose dead state would be (tag 0 = mix64(0) with
+//    a deleted token bucket) is written with c = kDeadMark, which no live token bucket has (c
+//    bit 0 clear = absent bucket). A sliding-window slot keeps two offsets in c, where 2 is an
+//    ordinary value; it is dead iff both counts are zero.
+// Who keeps it, and how:
+//  * A batch's region loaded as an LDS image (rl_region.hpp) loads in place: live keys keep
+//    their slots and dead ones stay as tombstones, in LDS (kOccTomb) and in HBM. Only once
+//    live + dead slots crowd the region (> kTombCrowd) are the dead ones dropped and the chains
+//    relinked, the whole region then being written back.
+//  * Sparse region waves (few records), the solo pass and rl_drop_keys touch single buckets and
+//    never free a slot inside a chain; the hot-chain rebuild writes its region whole.
+//  * The TTL sweep, the table shrink, state import, rl_put_keys(_device) and table growth stage a
+//    region's kept slots from their homes and write every slot of it (write_region,
+//    rl_table.hpp): dropped slots become zeros and the chains are rebuilt. Only these bring used
+//    slots back down to live keys.
 constexpr uint64_t kDeadMark = 2;
 __host__ __device__ inline bool slot_free(const Slot& v, uint64_t x = 0) {
     return (v.tag | v.a | v.b | v.c | x) == 0;
@@ -119,7 +131,9 @@ __host__ __device__ inline Slot slot_used(Slot v, uint64_t x = 0) {
 constexpr uint32_t kOccUsed = 1u;       // holds a key (live, or a tombstone with kOccTomb)
 constexpr uint32_t kOccTouched = 2u;    // read or written by this batch
 constexpr uint32_t kOccUnloaded = 4u;   // sparse region: bucket not fetched from HBM yet
-constexpr uint32_t kOccTomb = 8u;       // dead slot kept as a tombstone (claimable by an insert)
+constexpr uint32_t kOccTomb = 8u;       // dead slot kept as a tombstone, in sparse and in image regions
+                                        // alike (claimable by an insert, never a hit; an image
+                                        // region drops them once it is crowded, kTombCrowd)
 constexpr uint32_t kOccDirty = 16u;     // image region: changed by the load (dropped, moved)
 
 // ---------------------------------------------------------------- hashing

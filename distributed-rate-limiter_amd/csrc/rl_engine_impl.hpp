@@ -240,7 +240,8 @@ struct rl_engine {
     uint32_t digest_per_cu = 0;             // rl_tune("digest_per_cu"), 0 = default
     DevArray<uint8_t> snap;                 // snapshot / ordered-put scratch (snap_scratch_bytes), on first use
     DevArray<uint32_t> put_heads;           // run heads of an ordered put
-    DevArray<rl::KeyImage> img_stage;       // images of rl_snapshot_keys / rl_restore_keys
+    DevArray<rl::KeyImage> img_stage;       // images of rl_snapshot_keys / rl_restore_keys / rl_check_images
+    DevArray<unsigned long long> check_rep; // [kCrWords] the host forms' report of rl_check_*, on first use
     // string-key staging of rl_hash_keys / rl_execute_batch_keys, on first use
     size_t key_stage_bytes = (size_t)4 << 20;   // rl_tune("key_stage_bytes"): the blob stage's size
     DevArray<uint8_t> ks_blob;              // one chunk of key bytes

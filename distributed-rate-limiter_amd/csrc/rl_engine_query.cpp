@@ -1,6 +1,7 @@
 // rl_engine_query.cpp — the read-only queries of an engine: retry-after, heavy-hitter keys, the
-// batch report, the census of a limiter's table, string keys and the table digest.
+// batch report, the census of a limiter's table, string keys, the table digest and the table check.
 #include "rl_engine_impl.hpp"
+#include "rl_check.hpp"
 #include "rl_keys.hpp"
 #include "rl_report.hpp"
 
@@ -644,5 +645,150 @@ extern "C" int rl_limiter_digest(rl_engine* e, uint16_t limiter, int64_t now_ns,
         }
         *total = t;
     }
+    return RL_OK;
+}
+
+// ---------------------------------------------------------------- table check
+// rl_check.hip on the engine stream, under the census' rules (above): behind every batch
+// submitted before, the table as installed, no collect_status, nothing written but the report
+// (e->check_rep: the host forms' device-side report).
+static_assert(RL_CHECK_CLASSES == kCheckClasses && sizeof(rl_check_report) == kCrWords * 8 &&
+              sizeof(rl_check_report) == 312, "rl_check_report layout");
+static_assert(offsetof(rl_check_report, used_slots) == kCrUsed * 8 &&
+              offsetof(rl_check_report, bad_slots) == kCrBad * 8 &&
+              offsetof(rl_check_report, violations) == kCrViolations * 8 &&
+              offsetof(rl_check_report, first) == kCrFirst * 8, "rl_check_report field order");
+static_assert(RL_CHECK_WRONG_REGION == kCkWrongRegion && RL_CHECK_UNREACHABLE == kCkUnreachable &&
+              RL_CHECK_DUPLICATE == kCkDuplicate && RL_CHECK_DEAD_MARK == kCkDeadMark &&
+              RL_CHECK_SW_START == kCkSwStart && RL_CHECK_SW_COUNT == kCkSwCount &&
+              RL_CHECK_SW_OFFSET == kCkSwOffset && RL_CHECK_TB_FLAGS == kCkTbFlags &&
+              RL_CHECK_TB_TOKENS == kCkTbTokens && RL_CHECK_IMAGE_LIMITER == kCkImageLimiter &&
+              RL_CHECK_IMAGE_RESERVED == kCkImageReserved, "check class ids");
+constexpr uint32_t kCheckMinBits = kBinShift, kCheckMaxBits = 24;
+
+// The report set up and the pass over regions [begin, begin + count), clipped to the 2^bits
+// regions at `tab`, with limiter li's constants: both on the engine stream.
+static int check_enqueue(rl_engine* e, size_t li, const void* tab, const uint64_t* xtab, uint32_t bits,
+                         uint64_t begin, uint64_t count, unsigned long long* out) {
+    const DevLimiter& L = e->lims[li].dev;
+    const uint64_t total = 1ULL << bits;
+    CheckArgs a{};
+    a.tab = (const Slot*)tab; a.xtab = xtab;
+    a.region_begin = begin;
+    a.m = begin >= total ? 0 : std::min<uint64_t>(count, total - begin);
+    a.region_bits = (int32_t)bits; a.shard_bits = e->shard_bits;
+    a.algo = L.algo; a.window_ms = L.window_ms; a.ttl_ms = L.ttl_ms;
+    a.out = out;
+    HIP_OK(launch_check_init(out, a.m, a.m * kRegionSlots, e->stream));
+    HIP_OK(launch_check_regions(a, e->stream));
+    return RL_OK;
+}
+
+// (e->mu held) limiter li's own table; RL_E_INTERNAL if it is not 2^region_bits regions
+static int check_own_enqueue(rl_engine* e, size_t li, uint64_t begin, uint64_t count, unsigned long long* out) {
+    const HostLimiter& h = e->lims[li];
+    const uint32_t bits = (uint32_t)h.dev.region_bits;
+    if (h.table_bytes != ((size_t)kRegionSlots * sizeof(Slot)) << bits) return RL_E_INTERNAL;
+    return check_enqueue(e, li, h.table, (const uint64_t*)h.cache_table, bits, begin, count, out);
+}
+
+extern "C" int rl_check_limiter_device(rl_engine* e, uint16_t limiter, uint64_t region_begin,
+                                       uint64_t region_count, rl_check_report* out_dev, void* stream) {
+    if (!e || !out_dev || ((uintptr_t)out_dev & 7u)) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (limiter >= e->lims.size()) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    StreamJoin join(e->stream, (hipStream_t)stream);
+    HIP_OK(join.err);
+    const int rc = check_own_enqueue(e, limiter, region_begin, region_count, (unsigned long long*)out_dev);
+    if (rc != RL_OK) return rc;
+    HIP_OK(join.finish());
+    return RL_OK;
+}
+
+extern "C" int rl_check_limiter(rl_engine* e, uint16_t limiter, uint64_t region_begin,
+                                uint64_t region_count, rl_check_report* out) {
+    if (!e || !out) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (limiter >= e->lims.size()) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    int rc = e->check_rep.reserve(kCrWords);
+    if (rc != RL_OK) return rc;
+    rc = check_own_enqueue(e, limiter, region_begin, region_count, e->check_rep);
+    if (rc != RL_OK) return rc;
+    rl_check_report r;
+    HIP_OK(hipMemcpyAsync(&r, e->check_rep, sizeof(r), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    *out = r;
+    return RL_OK;
+}
+
+extern "C" int rl_check_table_device(rl_engine* e, uint16_t limiter, const void* slots,
+                                     const uint64_t* cache_words, uint32_t region_bits,
+                                     rl_check_report* out_dev, void* stream) {
+    if (!e || !slots || !out_dev || ((uintptr_t)slots & 15u) || ((uintptr_t)cache_words & 7u) ||
+        ((uintptr_t)out_dev & 7u) || region_bits < kCheckMinBits || region_bits > kCheckMaxBits)
+        return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (limiter >= e->lims.size()) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    StreamJoin join(e->stream, (hipStream_t)stream);
+    HIP_OK(join.err);
+    const int rc = check_enqueue(e, limiter, slots, cache_words, region_bits, 0, 1ULL << region_bits,
+                                 (unsigned long long*)out_dev);
+    if (rc != RL_OK) return rc;
+    HIP_OK(join.finish());
+    return RL_OK;
+}
+
+static int check_images_enqueue(rl_engine* e, size_t n, const KeyImage* in, uint64_t index_base,
+                                unsigned long long* out) {
+    CheckImgArgs a{};
+    a.in = in; a.n = n; a.index_base = index_base;
+    a.lims = e->d_lims; a.n_lim = (uint32_t)e->lims.size();
+    a.out = out;
+    HIP_OK(launch_check_images(a, e->stream));
+    return RL_OK;
+}
+
+extern "C" int rl_check_images_device(rl_engine* e, size_t n, const rl_key_image* in,
+                                      rl_check_report* out_dev, void* stream) {
+    if (!e || !out_dev || ((uintptr_t)out_dev & 7u) || (n && !in) || ((uintptr_t)in & 15u))
+        return RL_E_INVALID_ARG;
+    if ((uint64_t)n > kCheckMaxImages) return RL_E_TOO_LARGE;
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipSetDevice(e->device);
+    StreamJoin join(e->stream, (hipStream_t)stream);
+    HIP_OK(join.err);
+    HIP_OK(launch_check_init((unsigned long long*)out_dev, 0, n, e->stream));
+    const int rc = check_images_enqueue(e, n, (const KeyImage*)in, 0, (unsigned long long*)out_dev);
+    if (rc != RL_OK) return rc;
+    HIP_OK(join.finish());
+    return RL_OK;
+}
+
+extern "C" int rl_check_images(rl_engine* e, size_t n, const rl_key_image* in, rl_check_report* out) {
+    if (!e || !out || (n && !in)) return RL_E_INVALID_ARG;
+    if ((uint64_t)n > kCheckMaxImages) return RL_E_TOO_LARGE;
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipSetDevice(e->device);
+    // pieces of at most max_batch images through e->img_stage, as rl_restore_keys; every piece
+    // adds to the one report
+    const size_t piece = std::min<size_t>(n, (size_t)std::max<uint64_t>(e->opts.max_batch, 1));
+    int rc = e->check_rep.reserve(kCrWords);
+    if (rc == RL_OK) rc = e->img_stage.reserve(piece);
+    if (rc != RL_OK) return rc;
+    hipStream_t s = e->stream;
+    HIP_OK(launch_check_init(e->check_rep, 0, n, s));
+    for (size_t at = 0; at < n; at += piece) {
+        const size_t m = std::min(piece, n - at);
+        HIP_OK(hipMemcpyAsync(e->img_stage, in + at, m * sizeof(KeyImage), hipMemcpyHostToDevice, s));
+        rc = check_images_enqueue(e, m, e->img_stage, at, e->check_rep);
+        if (rc != RL_OK) { (void)hipStreamSynchronize(s); return rc; }
+    }
+    rl_check_report r;
+    HIP_OK(hipMemcpyAsync(&r, e->check_rep, sizeof(r), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    *out = r;
     return RL_OK;
 }

@@ -645,6 +645,32 @@ hipError_t launch_digest(const DigestArgs& a, hipStream_t s);
 constexpr uint32_t kDigestFineBits = 10;
 hipError_t launch_digest_fold(const BucketDigest* fine, uint32_t fine_bits, BucketDigest* out,
                               uint32_t bucket_bits, hipStream_t s);
+// Check of a table's slot invariants (rl_check.hip; rl_check_limiter(_device),
+// rl_check_table_device, rl_check_images(_device); the rules: rl_check.hpp). The report is
+// rl_check_report (include/rl_engine.h) as kCrWords 64-bit words; launch_check_init sets it up
+// on the stream, the passes add to it with atomics.
+enum : uint32_t { kCrRegions = 0, kCrSlots, kCrUsed, kCrState, kCrTomb, kCrCache, kCrBad,
+                  kCrViolations, kCrFirst = kCrViolations + 16, kCrWords = kCrFirst + 16 };
+struct CheckArgs {
+    const Slot* tab;               // 2^region_bits regions of kRegionSlots slots, 16-B aligned
+    const uint64_t* xtab;          // nullable: a cache word per slot
+    uint64_t region_begin, m;      // the regions [region_begin, region_begin + m), inside the table
+    int32_t region_bits, shard_bits;
+    int32_t algo;                  // the limiter's constants the value classes need
+    int64_t window_ms, ttl_ms;
+    unsigned long long* out;       // [kCrWords], 8-B aligned
+};
+struct CheckImgArgs {
+    const KeyImage* in;            // [n], 16-B aligned
+    uint64_t n;                    // <= 2^31
+    uint64_t index_base;           // first[] holds index_base + i (the host form's pieces)
+    const DevLimiter* lims;
+    uint32_t n_lim;
+    unsigned long long* out;       // [kCrWords]
+};
+hipError_t launch_check_init(unsigned long long* out, uint64_t regions, uint64_t slots, hipStream_t s);
+hipError_t launch_check_regions(const CheckArgs& a, hipStream_t s);
+hipError_t launch_check_images(const CheckImgArgs& a, hipStream_t s);
 // String keys hashed on the device (rl_keys.hip; rl_hash_keys(_device), rl_execute_batch_keys,
 // include/rl_engine.h): out[i] = rl_key_hash of the bytes [off[i] - bias, off[i + 1] - bias) of
 // `bytes`, or 0 for a key that is not well-formed within bytes_len (rl_keys.hpp), which is

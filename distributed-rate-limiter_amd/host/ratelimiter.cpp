@@ -236,6 +236,31 @@ rl_shrink_report GpuEngine::shrink(uint16_t limiter, int64_t nowNanos, uint64_t 
     return r;
 }
 
+rl_check_report GpuEngine::check(uint16_t limiter) {
+    rl_check_report r{};
+    int st;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        st = rl_check_limiter(e_, limiter, 0, ~0ULL, &r);
+    }
+    if (st == RL_E_INVALID_ARG) throw IllegalArgumentException(std::string("check: ") + rl_strerror(st));
+    if (st != RL_OK) throw StorageException(std::string("check: ") + rl_strerror(st), st);
+    return r;
+}
+
+rl_check_report GpuEngine::checkImages(const rl_key_image* images, size_t n) {
+    if (n && !images) throw IllegalArgumentException("checkImages: null images");
+    rl_check_report r{};
+    int st;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        st = rl_check_images(e_, n, images, &r);
+    }
+    if (st == RL_E_INVALID_ARG) throw IllegalArgumentException(std::string("checkImages: ") + rl_strerror(st));
+    if (st != RL_OK) throw StorageException(std::string("checkImages: ") + rl_strerror(st), st);
+    return r;
+}
+
 // Throws unless the limiter exists and its table has at least bucketBits region bits (so nothing
 // is sized by a bucketBits the engine would refuse); returns the table's region count.
 static uint64_t digestRegions(rl_engine* e, uint16_t limiter, uint32_t bucketBits, const char* what) {
@@ -487,6 +512,18 @@ std::vector<rl_bucket_digest> GpuRateLimiter::digest(uint32_t bucketBits) {
         ~Release() { lk.lock(); self->flushing_ = false; self->cv_.notify_all(); }
     } rel{this, lk};
     return engine_->digest(id_, now, bucketBits);
+}
+
+rl_check_report GpuRateLimiter::check() {
+    std::unique_lock<std::mutex> lk(mu_);
+    cv_.wait(lk, [&] { return !flushing_; });
+    flushing_ = true;
+    lk.unlock();
+    struct Release {
+        GpuRateLimiter* self; std::unique_lock<std::mutex>& lk;
+        ~Release() { lk.lock(); self->flushing_ = false; self->cv_.notify_all(); }
+    } rel{this, lk};
+    return engine_->check(id_);
 }
 
 rl_shrink_report GpuRateLimiter::compact() {

@@ -221,6 +221,14 @@ class GpuEngine {
                            const std::vector<rl_bucket_digest>& previous,
                            std::vector<rl_bucket_digest>* current, size_t chunkImages,
                            const BucketSink& sink);
+    // rl_check_limiter over the limiter's whole table: how many slots break which of the slot
+    // invariants, and where the first one is (bad_slots == 0: the table is sound). What
+    // redis-check-rdb answers for the reference's Redis; call it after a restore, a migration or
+    // an RL_E_INTERNAL. Read-only. IllegalArgumentException for an unknown limiter.
+    rl_check_report check(uint16_t limiter);
+    // rl_check_images: the value classes over images before they are restored (first[] holds
+    // image indices). Read-only.
+    rl_check_report checkImages(const rl_key_image* images, size_t n);
 
   private:
     rl_engine* e_ = nullptr;
@@ -272,6 +280,9 @@ class GpuRateLimiter : public RateLimiter {
     // its rejecting local-cache entries): compare with a replica's or a restored engine's, or
     // keep them for GpuEngine::snapshotChanged. Read-only; sees every tryAcquire that has returned.
     std::vector<rl_bucket_digest> digest(uint32_t bucketBits);
+    // Is this limiter's table sound (GpuEngine::check)? Read-only; sees every tryAcquire of this
+    // object that has returned.
+    rl_check_report check();
     // the reference's permits check (SlidingWindowRateLimiter.java:87-89,
     // TokenBucketRateLimiter.java:106-108): throws IllegalArgumentException for permits <= 0
     static void requirePositive(int permits);

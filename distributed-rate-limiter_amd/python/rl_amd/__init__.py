@@ -42,6 +42,12 @@ DIGEST_K = (0x9E3779B97F4A7C15, 0xC2B2AE3D27D4EB4F, 0x165667B19E3779F9)
 DIGEST_C1, DIGEST_C2 = 0xFF51AFD7ED558CCD, 0xC4CEB9FE1A85EC53
 KEY_MAX_BYTES = 4096                       # RL_KEY_MAX_BYTES: longest key of a string-key batch
 SNAPSHOT_MIN_CAP = 256                     # RL_SNAPSHOT_MIN_CAP: a snapshot cap that always makes progress
+CHECK_CLASSES = 16                         # RL_CHECK_CLASSES: class ids of a table check (RL_CHECK_*)
+(CHECK_WRONG_REGION, CHECK_UNREACHABLE, CHECK_DUPLICATE, CHECK_DEAD_MARK, CHECK_SW_START,
+ CHECK_SW_COUNT, CHECK_SW_OFFSET, CHECK_TB_FLAGS, CHECK_TB_TOKENS, CHECK_IMAGE_LIMITER,
+ CHECK_IMAGE_RESERVED) = range(11)         # (SW_COUNT, TB_TOKENS: reserved, never reported)
+CHECK_NONE = 0xFFFFFFFFFFFFFFFF            # rl_check_report.first: no such slot
+DEAD_MARK = 2                              # kDeadMark in csrc/rl_device.hpp
 SHRINK_FILL_MAX, SHRINK_LEVELS = 104, 24   # RL_SHRINK_* (rl_shrink_plan, rl_shrink_limiter)
 PUT_REJECT_ORDER, PUT_REJECT_LIMITER = 1, 2   # `rejected` bits of rl_put_keys_device's header
 OPT_STAGE_TIMING = 1
@@ -76,6 +82,8 @@ EXPORTS = [
     "rl_route_fold_ops", "rl_route_unfold_ops", "rl_route_unpack_wait",
     "rl_key_hash", "rl_hash_keys", "rl_hash_keys_device", "rl_execute_batch_keys",
     "rl_tally_batch", "rl_tally_batch_device", "rl_top_denied", "rl_top_denied_device",
+    "rl_check_limiter", "rl_check_limiter_device", "rl_check_table_device", "rl_check_images",
+    "rl_check_images_device",
 ]
 RCCL_EXPORTS = ["rl_rccl_unique_id", "rl_transport_rccl_create", "rl_transport_rccl_destroy"]
 STATE_SW_BUCKET, STATE_TB_BUCKET = 0, 1
@@ -151,6 +159,30 @@ class ShrinkReport(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("slots_before", "slots_after", "used_before", "kept")] + \
                [("halvings", ctypes.c_uint32), ("levels", ctypes.c_uint32),
                 ("fullest", ctypes.c_uint32 * SHRINK_LEVELS)]
+
+
+class CheckReport(ctypes.Structure):
+    """rl_check_report (include/rl_engine.h): what a table check found."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("regions", "slots", "used_slots", "state_slots",
+                                                 "tombstones", "cache_words", "bad_slots")] + \
+               [("violations", ctypes.c_uint64 * CHECK_CLASSES), ("first", ctypes.c_uint64 * CHECK_CLASSES)]
+
+
+CHECK_WORDS = 7 + 2 * CHECK_CLASSES
+assert ctypes.sizeof(CheckReport) == 8 * CHECK_WORDS == 312
+
+
+def check_dict(r) -> dict:
+    """A CheckReport, or its CHECK_WORDS 64-bit words (a device report copied back), as a dict;
+    `violations` and `first` as lists of CHECK_CLASSES values (first: CHECK_NONE = none)."""
+    if not isinstance(r, CheckReport):
+        w = np.ascontiguousarray(np.asarray(r).reshape(-1).view(np.uint64))
+        assert w.shape[0] == CHECK_WORDS
+        r = CheckReport.from_buffer_copy(w.tobytes())
+    d = {f: getattr(r, f) for f, _ in CheckReport._fields_[:7]}
+    d["violations"] = list(r.violations)
+    d["first"] = list(r.first)
+    return d
 
 
 class KeyImage(ctypes.Structure):
@@ -293,6 +325,11 @@ def lib():
                                                       ctypes.POINTER(ctypes.c_uint64),
                                                       ctypes.POINTER(ctypes.c_uint64)]
     L.rl_top_denied_device.argtypes = [vp, sz] + [vp] * 6 + [u16, u32, ctypes.c_uint64, vp, vp, vp, vp]
+    L.rl_check_limiter.argtypes = [vp, u16, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(CheckReport)]
+    L.rl_check_limiter_device.argtypes = [vp, u16, ctypes.c_uint64, ctypes.c_uint64, vp, vp]
+    L.rl_check_table_device.argtypes = [vp, u16, vp, vp, u32, vp, vp]
+    L.rl_check_images.argtypes = [vp, sz, vp, ctypes.POINTER(CheckReport)]
+    L.rl_check_images_device.argtypes = [vp, sz, vp, vp, vp]
     _lib = L
     return L
 
@@ -771,6 +808,53 @@ class Engine:
                                               DIGEST_CACHE if cache else 0, _p(out), _p(stream))
         if st != RL_OK:
             raise RlError(st, "rl_limiter_digest_device")
+
+    def check_limiter(self, limiter, region_begin=0, region_count=1 << 62) -> dict:
+        """Check the slot invariants of a limiter's table (rl_check_limiter) over the regions
+        [region_begin, region_begin + region_count), clipped to the table: a dict of the
+        rl_check_report fields (check_dict). bad_slots == 0: the range is sound. Read-only."""
+        r = CheckReport()
+        st = self._L.rl_check_limiter(self._h, int(limiter), int(region_begin), int(region_count),
+                                      ctypes.byref(r))
+        if st != RL_OK:
+            raise RlError(st, "rl_check_limiter")
+        return check_dict(r)
+
+    def check_limiter_device(self, limiter, region_begin, region_count, out, stream=None):
+        """rl_check_limiter_device: `out` is a device buffer of CHECK_WORDS x 8 bytes (a torch
+        tensor or a raw pointer, 8-byte aligned); asynchronous, ordered behind the batches
+        submitted before it."""
+        st = self._L.rl_check_limiter_device(self._h, int(limiter), int(region_begin),
+                                             int(region_count), _p(out), _p(stream))
+        if st != RL_OK:
+            raise RlError(st, "rl_check_limiter_device")
+
+    def check_table_device(self, limiter, slots, cache_words, region_bits, out, stream=None):
+        """rl_check_table_device: the same check over a caller-held device array of 2^region_bits
+        regions of 256 slots of 32 bytes (`cache_words`: one uint64 per slot, or None), with the
+        limiter's constants; asynchronous, `out` as for check_limiter_device."""
+        st = self._L.rl_check_table_device(self._h, int(limiter), _p(slots), _p(cache_words),
+                                           int(region_bits), _p(out), _p(stream))
+        if st != RL_OK:
+            raise RlError(st, "rl_check_table_device")
+
+    def check_images(self, images) -> dict:
+        """The value classes over host KEY_IMAGE_DTYPE images (rl_check_images): a dict as
+        check_limiter's, `first` holding image indices."""
+        images = np.ascontiguousarray(images, KEY_IMAGE_DTYPE)
+        r = CheckReport()
+        st = self._L.rl_check_images(self._h, images.shape[0], _p(images) if images.shape[0] else None,
+                                     ctypes.byref(r))
+        if st != RL_OK:
+            raise RlError(st, "rl_check_images")
+        return check_dict(r)
+
+    def check_images_device(self, n, images, out, stream=None):
+        """rl_check_images_device: n device images (16-byte aligned), `out` as for
+        check_limiter_device; asynchronous."""
+        st = self._L.rl_check_images_device(self._h, int(n), _p(images), _p(out), _p(stream))
+        if st != RL_OK:
+            raise RlError(st, "rl_check_images_device")
 
     def export_state(self, now_ns):
         """Live state at now_ns in the Redis layout: a STATE_DTYPE array (rl_export_state)."""

@@ -736,6 +736,101 @@ int  rl_limiter_digest(rl_engine* e, uint16_t limiter, int64_t now_ns, uint32_t 
 int  rl_limiter_digest_device(rl_engine* e, uint16_t limiter, int64_t now_ns, uint32_t bucket_bits,
                               uint32_t flags, rl_bucket_digest* out /* DEVICE */, void* stream);
 
+/* ---- table check: is this table sound? ---------------------------------------------
+ * What redis-check-rdb answers for the reference's Redis: a read-only device pass over a
+ * limiter's table (or over a list of images) that counts the slots breaking the rules every
+ * kernel relies on, per rule, and reports where the first such slot is. Use it after a restore
+ * from a file, a migration or an RL_E_INTERNAL; it repairs nothing.
+ * The rules, for region r of a table with k region bits and 256 slots per region; a slot is USED
+ * iff its four words and its local-cache word are not all zero:
+ *   structural (whatever wrote the table)
+ *   RL_CHECK_WRONG_REGION  a used slot whose tag = mix64(key_hash) does not hash to region r
+ *                          (shard ownership is not checked: the owner directory moves keys)
+ *   RL_CHECK_UNREACHABLE   a used slot s with a free slot in the cyclic range [home(tag), s),
+ *                          home = tag & 252: a lookup stops at that free slot, reports the key
+ *                          absent, and the key restarts with a full quota
+ *   RL_CHECK_DUPLICATE     a used slot whose tag also sits in a used slot of the region with a
+ *                          lower index, both holding bucket state, neither of which had expired
+ *                          (last write + ttl, ttl = window_ms / 2 x window_ms for a token bucket)
+ *                          before the other was last written; n such copies count n - 1. (A key
+ *                          that returns after its TTL may leave its expired slot behind the slot
+ *                          it claimed: two slots, ordered in time, and no violation.)
+ *   RL_CHECK_DEAD_MARK     token bucket: word[2] == 2 (the mark that keeps the dead slot of
+ *                          key_hash 0 from reading as free) on any other slot
+ *   values (state no entry point produces from inputs it accepts)
+ *   RL_CHECK_SW_START      sliding window, state present: newest bucket start % window_ms != 0
+ *   RL_CHECK_SW_OFFSET     sliding window: a bucket with a non-zero count whose last-INCR offset
+ *                          is outside (-window_ms, window_ms) (negative only for now < 0)
+ *   RL_CHECK_TB_FLAGS      token bucket: word[2] has bits other than bit 0 and is not the mark
+ *   RL_CHECK_SW_COUNT and RL_CHECK_TB_TOKENS are reserved ids and never reported:
+ *   rl_import_state admits any bucket count in [1, 2^32) and any double as a balance, so a count
+ *   above max_permits or a balance outside [0, capacity] is not proof of corruption.
+ *   image lists only
+ *   RL_CHECK_IMAGE_LIMITER   the engine has no limiter with the image's id (its values are not
+ *                            checked)
+ *   RL_CHECK_IMAGE_RESERVED  a non-zero reserved field
+ * A slot may count in several classes; ids without a rule read 0 / ~0.
+ *
+ * Common rules, as for the census: every call only reads (no limiter state, cache word, batch
+ * statistic, and not the status rl_last_status reports, which it does not collect either), works
+ * on the table as installed, and runs on the engine's stream behind every batch submitted before
+ * it (RL_OPT_PIPELINE included). The host forms synchronise; the device forms are enqueued
+ * (joined with `stream` as the other *_device calls, NULL = the engine's) and return argument or
+ * launch status only, the whole report being written on the stream. RL_E_INVALID_ARG, before any
+ * device call and with the outputs untouched: a null engine (checked first), an unknown limiter,
+ * a null report, a device report that is not 8-byte aligned, a device table or image array that
+ * is not 16-byte aligned, cache words that are not 8-byte aligned, region_bits outside [3, 24],
+ * n > 0 with a null `in`. RL_E_TOO_LARGE: n > 2^31. Device memory: one 312-byte report (and the
+ * host form's staged images, min(n, rl_opts.max_batch) x 48 B), allocated by the first call and
+ * freed by rl_destroy. Multi-GPU: an engine checks its own shard. */
+#define RL_CHECK_CLASSES 16
+#define RL_CHECK_WRONG_REGION    0
+#define RL_CHECK_UNREACHABLE     1
+#define RL_CHECK_DUPLICATE       2
+#define RL_CHECK_DEAD_MARK       3
+#define RL_CHECK_SW_START        4
+#define RL_CHECK_SW_COUNT        5   /* reserved: not checked */
+#define RL_CHECK_SW_OFFSET       6
+#define RL_CHECK_TB_FLAGS        7
+#define RL_CHECK_TB_TOKENS       8   /* reserved: not checked */
+#define RL_CHECK_IMAGE_LIMITER   9
+#define RL_CHECK_IMAGE_RESERVED 10
+typedef struct rl_check_report {            /* 312 bytes */
+    uint64_t regions, slots;                /* checked (an image list: 0, n)                      */
+    uint64_t used_slots;                    /* == rl_usage.used_slots over the same range          */
+    uint64_t state_slots;                   /* slots that hold state or a cache word: the images
+                                               rl_snapshot_keys emits for the range                */
+    uint64_t tombstones;                    /* used_slots - state_slots                            */
+    uint64_t cache_words;                   /* non-zero cache words                                */
+    uint64_t bad_slots;                     /* slots with >= 1 violation                           */
+    uint64_t violations[RL_CHECK_CLASSES];  /* slots per class                                     */
+    uint64_t first[RL_CHECK_CLASSES];       /* lowest region << 8 | slot per class (an image list:
+                                               lowest index), ~0: none; region = index in the table */
+} rl_check_report;
+/* The regions [region_begin, region_begin + region_count) of `limiter`, clipped to the table.
+ * region_begin at or beyond the table: RL_OK, a zeroed report with first[] = ~0. One pass over
+ * the range's slots (32 B each, + 8 B with a cache table). */
+int  rl_check_limiter(rl_engine* e, uint16_t limiter, uint64_t region_begin, uint64_t region_count,
+                      rl_check_report* out /* HOST */);
+int  rl_check_limiter_device(rl_engine* e, uint16_t limiter, uint64_t region_begin,
+                             uint64_t region_count, rl_check_report* out_dev, void* stream);
+/* The same pass over a caller-held DEVICE array laid out as a table, 2^region_bits regions of 256
+ * slots of 32 bytes {tag, word[3]}, with limiter `limiter`'s constants and the engine's shard
+ * bits: a copy of a table someone holds, or a synthetic one. cache_words (nullable): one uint64
+ * per slot. Exactly those bytes are read and nothing else; nothing read from them is used as an
+ * address, so any contents are safe to check. */
+int  rl_check_table_device(rl_engine* e, uint16_t limiter, const void* slots,
+                           const uint64_t* cache_words, uint32_t region_bits,
+                           rl_check_report* out_dev, void* stream);
+/* The value classes over n images, each with its limiter's constants, and the two image classes;
+ * first[] holds image indices, regions = 0, slots = n, used_slots = images that are not all zero
+ * (tag included), state_slots = those of a known limiter that hold state or a cache word. The
+ * structural classes need a table and do not apply. The host form stages pieces of at most
+ * rl_opts.max_batch images. */
+int  rl_check_images(rl_engine* e, size_t n, const rl_key_image* in /* HOST */, rl_check_report* out);
+int  rl_check_images_device(rl_engine* e, size_t n, const rl_key_image* in /* DEVICE */,
+                            rl_check_report* out_dev, void* stream);
+
 /* ---- string keys: one definition of the key hash, computed on the host or the device ------
  * key_hash everywhere in this header is rl_key_hash of the String key's UTF-8 bytes: FNV-1a 64
  * followed by mix64, the splitmix64 finaliser (above). All arithmetic is uint64 and wrapping;
