@@ -8,6 +8,7 @@
 // This unit: create and destroy, limiters and their growth, rl_tune, rl_sync, statistics and
 // stage times, rl_debug_fetch, pinned host buffers. Batches: rl_engine_batch.cpp; queries:
 // rl_engine_query.cpp; routing: rl_engine_route.cpp; table state: rl_engine_state.cpp.
+#include <atomic>
 #include <cmath>
 #include <new>
 
@@ -31,6 +32,28 @@ static void ensure_events(rl_engine* e) {
     if (e->ev[0][0]) return;
     for (int r = 0; r < kEvRing; ++r)
         for (int i = 0; i < kMarks; ++i) (void)hipEventCreate(&e->ev[r][i]);
+}
+
+// rl_debug_alloc_fill: -1 off, else the byte every new device allocation is filled with.
+static std::atomic<int> g_alloc_fill{-1};
+
+namespace rl {
+hipError_t dev_malloc(void** p, size_t bytes) {
+    hipError_t he = hipMalloc(p, bytes);
+    const int fill = g_alloc_fill.load(std::memory_order_relaxed);
+    if (he == hipSuccess && fill >= 0) {
+        he = hipMemset(*p, fill, bytes);           // (synchronous: done before any later use)
+        if (he == hipSuccess) he = hipDeviceSynchronize();
+        if (he != hipSuccess) { (void)hipFree(*p); *p = nullptr; }
+    }
+    return he;
+}
+}  // namespace rl
+
+extern "C" int rl_debug_alloc_fill(int byte) {
+    if (byte < -1 || byte > 255) return RL_E_INVALID_ARG;
+    g_alloc_fill.store(byte, std::memory_order_relaxed);
+    return RL_OK;
 }
 
 extern "C" int rl_abi_version(void) { return RL_ABI_VERSION; }
@@ -110,6 +133,10 @@ extern "C" int rl_create(const rl_opts* opts, rl_engine** out) {
         if (rc == RL_OK) rc = B.d_ctl.reserve(1);
         if (rc == RL_OK) rc = B.bin_total.reserve(1u << kMaxDigitBits);
         if (rc == RL_OK) rc = B.bin_base.reserve(1u << kMaxDigitBits);
+        // a batch writes its nb0 pass-0 bins only; rl_debug_fetch("bin_totals") copies all of them
+        if (rc == RL_OK && (hipMemset(B.bin_total, 0, sizeof(uint32_t) << kMaxDigitBits) != hipSuccess ||
+                            hipMemset(B.bin_base, 0, sizeof(uint32_t) << kMaxDigitBits) != hipSuccess))
+            rc = RL_E_DEVICE;
         if (rc == RL_OK && e->pipeline &&
             (hipEventCreateWithFlags(&B.parted, hipEventDisableTiming) != hipSuccess ||
              hipEventCreateWithFlags(&B.freed, hipEventDisableTiming) != hipSuccess))
@@ -485,6 +512,10 @@ extern "C" int rl_tune(rl_engine* e, const char* key, int64_t value) {
         e->walk_min = (uint32_t)value;
         return RL_OK;
     }
+    if (std::strcmp(key, "hot_epoch") == 0) {         // the hot marks' epoch as is (tests of its wrap)
+        e->epoch = (uint32_t)value;
+        return RL_OK;
+    }
     if (std::strcmp(key, "fail_batches") == 0) {      // the next `value` batches fail (RL_E_DEVICE)
         if (value < 0 || value > 0xFFFFFFFFLL) return RL_E_INVALID_ARG;
         e->inject_fail = (uint32_t)value;
@@ -521,6 +552,13 @@ extern "C" int rl_debug_fetch(rl_engine* e, const char* what, void* out, size_t 
         const size_t nb = std::min(bytes, ((size_t)1 << kMaxDigitBits) * sizeof(uint32_t));
         HIP_OK(hipMemcpy(out, B.bin_total, nb, hipMemcpyDeviceToHost));
         return (int)(nb / sizeof(uint32_t));
+    }
+    if (std::strcmp(what, "alloc_probe") == 0) {     // a fresh allocation as dev_malloc hands it out
+        if (bytes == 0 || bytes > ((size_t)1 << 20)) return RL_E_INVALID_ARG;
+        DevArray<uint8_t> probe;
+        if (probe.reserve(bytes) != RL_OK) return RL_E_NOMEM;
+        HIP_OK(hipMemcpy(out, probe, bytes, hipMemcpyDeviceToHost));
+        return (int)bytes;
     }
     if (std::strcmp(what, "usage_passes") == 0) {    // table passes of the last rl_top_consumers
         if (bytes < sizeof(uint32_t)) return RL_E_INVALID_ARG;

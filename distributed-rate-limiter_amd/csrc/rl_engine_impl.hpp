@@ -34,7 +34,7 @@ inline void dfree(void*& p) {
     p = nullptr;
 }
 inline int dalloc(void** p, size_t bytes) {
-    if (hipMalloc(p, bytes ? bytes : 16) != hipSuccess) {
+    if (rl::dev_malloc(p, bytes ? bytes : 16) != hipSuccess) {
         *p = nullptr;
         return RL_E_NOMEM;
     }

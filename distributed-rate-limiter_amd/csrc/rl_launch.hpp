@@ -790,5 +790,8 @@ size_t engine_directory(rl_engine* e, uint64_t* keys, uint32_t* owners);
 // status those batches return together, with the table growth they asked for applied once.
 int engine_status_accum(rl_engine* e, unsigned long long* acc, void* stream);
 int engine_status_settle(rl_engine* e, const unsigned long long* acc_host);
+// Every device allocation of the engine units and the router (dalloc, DevArray::reserve, the
+// router's buffers): hipMalloc, then filled with rl_debug_alloc_fill's byte while that is on.
+hipError_t dev_malloc(void** p, size_t bytes);
 
 }  // namespace rl

@@ -148,7 +148,7 @@ extern "C" int rl_router_create_ex(rl_engine* e, uint32_t world, uint32_t rank, 
     uint64_t bytes = 0;
     auto take = [&](auto** p, size_t b) {
         bytes += b;
-        return hipMalloc((void**)p, std::max<size_t>(b, 8)) == hipSuccess;
+        return dev_malloc((void**)p, std::max<size_t>(b, 8)) == hipSuccess;
     };
     r->ret_out_cap = ret_bound(world, m);
     r->ret_in_cap = ret_bound(world, n);
@@ -631,8 +631,8 @@ static int replan(rl_router* r, size_t n, const uint64_t* key, const uint64_t* c
     for (uint32_t p = 0; p < G; ++p) n_recv += rc[p];
     DevBuf b_send, b_recv;                           // (freed on every way out)
     (void)hipSetDevice(engine_device(e));
-    if (hipMalloc(&b_send.p, std::max<size_t>(n_img, 1) * sizeof(rl_key_image)) != hipSuccess ||
-        hipMalloc(&b_recv.p, std::max<size_t>(n_recv, 1) * sizeof(rl_key_image)) != hipSuccess)
+    if (dev_malloc(&b_send.p, std::max<size_t>(n_img, 1) * sizeof(rl_key_image)) != hipSuccess ||
+        dev_malloc(&b_recv.p, std::max<size_t>(n_recv, 1) * sizeof(rl_key_image)) != hipSuccess)
         local = worse(local, RL_E_NOMEM);
     rl_key_image* d_send = (rl_key_image*)b_send.p;
     rl_key_image* d_recv = (rl_key_image*)b_recv.p;

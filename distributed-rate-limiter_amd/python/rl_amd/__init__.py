@@ -83,7 +83,7 @@ EXPORTS = [
     "rl_key_hash", "rl_hash_keys", "rl_hash_keys_device", "rl_execute_batch_keys",
     "rl_tally_batch", "rl_tally_batch_device", "rl_top_denied", "rl_top_denied_device",
     "rl_check_limiter", "rl_check_limiter_device", "rl_check_table_device", "rl_check_images",
-    "rl_check_images_device",
+    "rl_check_images_device", "rl_debug_alloc_fill",
 ]
 RCCL_EXPORTS = ["rl_rccl_unique_id", "rl_transport_rccl_create", "rl_transport_rccl_destroy"]
 STATE_SW_BUCKET, STATE_TB_BUCKET = 0, 1
@@ -330,12 +330,21 @@ def lib():
     L.rl_check_table_device.argtypes = [vp, u16, vp, vp, u32, vp, vp]
     L.rl_check_images.argtypes = [vp, sz, vp, ctypes.POINTER(CheckReport)]
     L.rl_check_images_device.argtypes = [vp, sz, vp, vp, vp]
+    L.rl_debug_alloc_fill.argtypes = [ctypes.c_int]
     _lib = L
     return L
 
 
 def strerror(status: int) -> str:
     return lib().rl_strerror(int(status)).decode()
+
+
+def debug_alloc_fill(byte):
+    """Test hook (rl_debug_alloc_fill), process-wide: fill every device allocation the library
+    makes from now on with `byte` (0..255) before it is used; None turns the fill off."""
+    st = lib().rl_debug_alloc_fill(-1 if byte is None else int(byte))
+    if st != RL_OK:
+        raise RlError(st, "rl_debug_alloc_fill")
 
 
 def _p(a):
@@ -1042,9 +1051,19 @@ class Engine:
         return out[:k]
 
     def debug_bin_totals(self):
-        """The last batch's pass-0 bin sizes (2^kMaxDigitBits entries; the unused ones stale)."""
+        """The last batch's pass-0 bin sizes (2^kMaxDigitBits entries; beyond the batch's own bins
+        zero, or an earlier, wider batch's)."""
         out = np.zeros(1 << 13, np.uint32)
         k = self._L.rl_debug_fetch(self._h, b"bin_totals", _p(out), out.nbytes)
+        if k < 0:
+            raise RlError(k, "rl_debug_fetch")
+        return out[:k]
+
+    def debug_alloc_probe(self, nbytes=4096):
+        """A fresh device allocation of nbytes as the library's allocator hands it out
+        (rl_debug_fetch "alloc_probe"): with debug_alloc_fill on, every byte is the fill."""
+        out = np.zeros(int(nbytes), np.uint8)
+        k = self._L.rl_debug_fetch(self._h, b"alloc_probe", _p(out), out.nbytes)
         if k < 0:
             raise RlError(k, "rl_debug_fetch")
         return out[:k]

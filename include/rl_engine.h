@@ -378,14 +378,26 @@ int  rl_sync(rl_engine* e);
  * stage of rl_hash_keys / rl_execute_batch_keys, default 4 MiB, at least RL_KEY_MAX_BYTES) and
  * "keys_direct" (the key-hash kernel's workgroups all take the direct-read path, default 0).
  * Every setting gives the same decisions. "fail_batches" = k makes the next k batch
- * calls fail with RL_E_DEVICE before enqueuing anything (tests of callers' error paths). */
+ * calls fail with RL_E_DEVICE before enqueuing anything (tests of callers' error paths);
+ * "hot_epoch" = v sets the hot marks' epoch counter as is (tests of its wrap-around); the
+ * counter restarts at 0 whenever the marks are (re)allocated (the first hot batch, the first
+ * one after the region count grew), so set it after a hot batch on the table in question. */
 int  rl_tune(rl_engine* e, const char* key, int64_t value);
 /* Diagnostics (not needed by callers). "region_times": after a batch run with
  * rl_tune("debug_regions", 1), copies per-bin {t_start, t_end, records, rounds, cycle
  * counters} (uint64 x28 per bin; s_memrealtime ticks; rounds bit 63 = a hot region).
  * Returns the number of bins copied (>= 0) or a status < 0. "usage_passes": one uint32, the
- * table passes of the last rl_top_consumers call (digit passes + the compaction); returns 1. */
+ * table passes of the last rl_top_consumers call (digit passes + the compaction); returns 1.
+ * "alloc_probe" (tests of rl_debug_alloc_fill): makes a fresh device allocation of `bytes`
+ * bytes (at most 1 MiB) the way every buffer of the library is made, copies it out as it was
+ * handed over and frees it; returns `bytes`. */
 int  rl_debug_fetch(rl_engine* e, const char* what, void* out, size_t bytes);
+/* ---- debug (tests only) ----
+ * Process-wide: with byte in 0..255 every device allocation the library makes from then on
+ * (engines, limiter tables, routers) is filled with that byte before it is used; -1 (the
+ * default) turns the fill off. The library's own initialisations come after the fill. Costs
+ * nothing per batch either way; a test of "every word is written before it is read". */
+int  rl_debug_alloc_fill(int byte);
 const char* rl_strerror(int status);
 int  rl_abi_version(void);
 
