@@ -424,7 +424,9 @@ extern "C" int rl_stage_times(rl_engine* e, const char** names, float* ms, int c
 extern "C" int rl_tune(rl_engine* e, const char* key, int64_t value) {
     if (!e || !key) return RL_E_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
+#if RL_MEASURE   // (rl_launch.hpp) a key of the measurement build only
     if (std::strcmp(key, "ablate") == 0) { e->ablate = (uint32_t)value; return RL_OK; }
+#endif
     if (std::strcmp(key, "upsweep_per_cu") == 0) { e->tune.up_per_cu = (uint32_t)value; return RL_OK; }
     if (std::strcmp(key, "scatter_per_cu") == 0) { e->sc_per_cu = (uint32_t)value; return RL_OK; }
     if (std::strcmp(key, "scatter_split") == 0) { e->sc_split = value != 0; return RL_OK; }

@@ -220,7 +220,7 @@ struct rl_engine {
     uint32_t hot_hint = 0xFFFFFFFFu;        // hot regions of the last batch seen complete
     int last_status = RL_OK;
     uint64_t last_n = 0;
-    uint32_t ablate = 0;                    // rl_tune("ablate"), measurement only
+    uint32_t ablate = 0;                    // measurement build: rl_tune("ablate"); else 0
     uint32_t sc_per_cu = 0, un_per_cu = 0;  // rl_tune("*_per_cu"), 0 = default
     uint32_t sc_split = 1;                  // rl_tune("scatter_split"): k_scatter_split
     uint32_t un_split = 2;                  // rl_tune("unpermute_split"): k_unpermute_split

@@ -202,7 +202,7 @@ __global__ __launch_bounds__(kGroupThreads) void k_gplace(GroupArgs a) {
                 wave_fence();                            // every lane has read its cursor
                 if (act && lr == 0) cw[sb] = pos + (uint32_t)__popcll(m);
                 wave_fence();
-                const uint32_t wp = (a.ablate & kAblGroupSeq) ? i : pos;
+                const uint32_t wp = (RL_ABLATION(a) & kAblGroupSeq) ? i : pos;
                 st_rec<false>(out + (act ? wp : pad), r[k]);    // (temporal: sectors merge in L2)
                 st<kNtScPos>(a.pos_out + (act ? i : pad), act ? pos : 0u);
             }
@@ -345,7 +345,7 @@ hipError_t launch_group(const GroupArgs& a, bool wide, hipStream_t s) {
     if (wide) hipLaunchKernelGGL(k_gcount<CodecW>, gw, b, lds, s, a);
     else hipLaunchKernelGGL(k_gcount<CodecC>, gw, b, lds, s, a);
     hipLaunchKernelGGL(k_gscan, dim3(a.n_bins0), b, nsub * sizeof(uint32_t), s, a);
-    if (a.sub_bits <= kGLdsMaxSub && !(a.ablate & kAblGroupSeq)) {
+    if (a.sub_bits <= kGLdsMaxSub && !(RL_ABLATION(a) & kAblGroupSeq)) {
         const dim3 gp(persistent_grid((a.max_tiles + 1) / 2, 4)), bp(kGPThreads);
         if (wide) hipLaunchKernelGGL(k_gplace_lds<CodecW>, gp, bp, gplace_lds_bytes<RecW>(a.sub_bits), s, a);
         else hipLaunchKernelGGL(k_gplace_lds<CodecC>, gp, bp, gplace_lds_bytes<RecC>(a.sub_bits), s, a);

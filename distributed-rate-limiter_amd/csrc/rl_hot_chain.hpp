@@ -167,7 +167,7 @@ RL_PART void chain_pass2(Env& e) {
         uint32_t n_hits = 0;                          // (no local cache on the hot path)
         const Applied ap = wave_apply<Codec, A, false>(a, e.S, e.L, lane, e.S.ring[ri], v, e.S.ring_pos[ri], e.base,
                                                 pad, e.n_allowed, e.n_invalid, e.n_caperr, e.n_rounds, n_hits, sp);
-        if (v && !(a.ablate & kAblNoChainStores)) {
+        if (v && !(RL_ABLATION(a) & kAblNoChainStores)) {
             put_res<typename Env::Res>(a, ap.j, ap.alw, ap.rem);
             if (Env::TOK) a.tok[ap.j] = ap.tok;
         }

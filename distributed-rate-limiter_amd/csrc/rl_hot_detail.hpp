@@ -563,7 +563,7 @@ RL_PART void detail(KC& k, uint32_t c, int64_t mn_l, int64_t mx_l, uint32_t ns_l
         dbg.cyc_run += c_srch - c_run;
         dbg.cyc_search += c_end - c_srch;
     }
-    if (d.hot && !(a.ablate & kAblNoChainStores)) {
+    if (d.hot && !(RL_ABLATION(a) & kAblNoChainStores)) {
         put_res<typename Env::Res>(a, j, d.oa, d.orem);
         if (Env::TOK) a.tok[j] = d.tk;
     }

@@ -9,7 +9,21 @@ struct rl_engine;   // include/rl_engine.h
 
 namespace rl {
 
-// Ablation bits (rl_tune "ablate"): timing experiments only; results are wrong when set.
+// RL_MEASURE=1 builds the measurement library (tools/build_variant.sh measure "-DRL_MEASURE=1"):
+// rl_tune gains the key "ablate", whose bits switch kernels to variants that are wrong by
+// design. The product library (0) has no such key and none of those variants: every read of an
+// `ablate` word, on the device and in the launchers, is RL_ABLATION(args), the constant 0 there,
+// so the branches fold away. The words themselves stay in the argument structs (always 0 in
+// the product): one struct layout, and no conditional line beyond the two places that name
+// things the product must not have (rl_tune's key, the k_scatter_split<CodecC, ABL> kernels).
+// (A macro, not an inline function: the measurement build's device code is then the text the
+// compiler saw before the switch existed, byte for byte.)
+#ifndef RL_MEASURE
+#define RL_MEASURE 0
+#endif
+#define RL_ABLATION(a) (RL_MEASURE ? (a).ablate : 0u)
+
+// Ablation bits (measurement build only): timing experiments; results are wrong when set.
 enum : uint32_t {
     kAblNoRecStore = 1u << 0,    // scatter: skip the record store
     kAblSeqRecStore = 1u << 1,   // scatter: store records at their input index (coalesced)
@@ -86,7 +100,7 @@ struct PartArgs {
     const uint32_t* seg_adj;
     uint32_t n_segs, seg_tiles;
     BatchCtl* ctl;
-    uint32_t ablate;           // rl_tune("ablate"): measurement-only variants (0 = product)
+    uint32_t ablate;           // measurement build: rl_tune("ablate"); 0 in the product
     uint32_t n_bins_pass;      // bins of this pass (0: 1 << digit_bits)
     // Hot-region routing (pass 0 of a two-pass batch): route_list is a kRouteSlots-entry
     // table of region ids (kNone = empty; the previous batch's largest hot regions, each at
@@ -262,7 +276,7 @@ struct GroupArgs {
     uint32_t* tile_beg;
     uint32_t* tile_end;
     uint32_t pad;              // the batch size: rec_out / pos_out hold 64 padding entries past it
-    uint32_t ablate;           // rl_tune("ablate") (measurement only)
+    uint32_t ablate;           // measurement build: rl_tune("ablate"); 0 in the product
 };
 // records per tile of the grouping: 8192, or 32 per region of a bin when bins are wide
 __host__ __device__ inline uint32_t group_tile_recs(uint32_t sub_bits) {

@@ -305,7 +305,7 @@ __global__ __launch_bounds__(kTileThreads) void k_scatter(PartArgs a) {
             Rec rec;
             uint32_t d;
             encode_request<Codec>(a, L, base, in, i, n, tr, rec, d);
-            const uint32_t abl = a.ablate;
+            const uint32_t abl = RL_ABLATION(a);
             uint32_t pos = rank_round(cntw, cur, d, a.digit_bits, active, lane, wid,
                                       abl & kAblNoMatch, abl & kAblNoBarrier);
             if (abl & (kAblNoMatch | kAblNoBarrier)) pos = min(pos, n - 1);
@@ -342,7 +342,7 @@ __global__ __launch_bounds__(kTileThreads) void k_scatter(PartArgs a) {
 // waves (threads 0..kTileThreads-1) read them from LDS, rank, and store — they issue no
 // global load inside a tile, so nothing ever waits behind their stores.
 constexpr int kSplitDepth = 4;       // loader rounds in flight (divides tile_items)
-// ABL (measurement-only instantiations, rl_tune ablate bits 20-25; results wrong): 1 no record
+// ABL (the measurement build's instantiations, its rl_tune ablate bits 20-25; results wrong): 1 no record
 // store, 2 no position store, 4 records stored at their input index, 8 no ballot match,
 // 16 no encode (the key as the record, digit 0 + lane), 32 whole sectors (each lane its
 // record to both halves of its 32-B sector)
@@ -528,10 +528,12 @@ hipError_t launch_upsweep(const PartArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+#if RL_MEASURE   // the k_scatter_split<CodecC, ABL != 0> kernels exist in the measurement build only
 template <int ABL>
 static void scatter_split_abl(const PartArgs& a, dim3 grid, size_t lds, hipStream_t s) {
     hipLaunchKernelGGL((k_scatter_split<CodecC, ABL>), grid, dim3(2 * kTileThreads), lds, s, a);
 }
+#endif
 
 hipError_t launch_scatter(const PartArgs& a, bool wide, hipStream_t s) {
     dim3 grid(persistent_grid(a.n_tiles, a.sc_per_cu ? a.sc_per_cu : 1)), block(kTileThreads);
@@ -539,8 +541,9 @@ hipError_t launch_scatter(const PartArgs& a, bool wide, hipStream_t s) {
     if (bins > (1u << kMaxDigitBits)) return hipErrorInvalidValue;
     const dim3 b2(2 * kTileThreads);
     const size_t lc = scatter_split_lds_bytes<CodecC>(bins), lw = scatter_split_lds_bytes<CodecW>(bins);
-    if (a.sc_split && (a.ablate >> 20) && !wide) {   // measurement-only variants
-        switch ((a.ablate >> 20) & 63u) {
+#if RL_MEASURE
+    if (a.sc_split && (RL_ABLATION(a) >> 20) && !wide) {
+        switch ((RL_ABLATION(a) >> 20) & 63u) {
             case 1: scatter_split_abl<1>(a, grid, lc, s); break;
             case 2: scatter_split_abl<2>(a, grid, lc, s); break;
             case 3: scatter_split_abl<3>(a, grid, lc, s); break;
@@ -551,7 +554,9 @@ hipError_t launch_scatter(const PartArgs& a, bool wide, hipStream_t s) {
             case 32: scatter_split_abl<32>(a, grid, lc, s); break;
             default: return hipErrorInvalidValue;
         }
-    } else if (a.sc_split && !a.ablate) {
+    } else
+#endif
+    if (a.sc_split && !RL_ABLATION(a)) {
         if (wide) hipLaunchKernelGGL((k_scatter_split<CodecW>), grid, b2, lw, s, a);
         else hipLaunchKernelGGL((k_scatter_split<CodecC>), grid, b2, lc, s, a);
     } else {

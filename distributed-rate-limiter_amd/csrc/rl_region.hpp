@@ -46,7 +46,7 @@ struct RegionLds<Codec, false> : RegionTable {};
 constexpr uint32_t kTombCrowd = 192;
 // Token-bucket rounds: allows decided per key and round (wave_apply)
 constexpr int kTbSteps = 3;
-constexpr bool kSparseOn = true;                 // (rl_tune ablate kAblNoProbe turns it off at run time)
+constexpr bool kSparseOn = true;                 // (measurement build: kAblNoProbe turns it off at run time)
 
 // Sparse region (few records): the LDS table starts with every bucket kOccUnloaded and a
 // probe that reaches such a bucket faults it in from HBM (128 B, + 32 B of cache words);
@@ -167,7 +167,7 @@ __device__ inline Applied wave_apply(const RegionArgs& a, LdsT& S, const DevLimi
     int32_t slot = -1;
     bool need = live, failed = false;
     const uint32_t home = slot_home(q.h);
-    if (a.ablate & kAblNoProbe) { if (need) slot = (int32_t)home; need = false; }
+    if (RL_ABLATION(a) & kAblNoProbe) { if (need) slot = (int32_t)home; need = false; }
     for (;;) {
         if (!__any(need)) break;
         ++sp.n_probe;
@@ -250,7 +250,7 @@ __device__ inline Applied wave_apply(const RegionArgs& a, LdsT& S, const DevLimi
     // up to and including the first denied request is final. The longer prefix is taken,
     // so a run of denials or a run of allows costs one round, not one per request.
     // my key's lanes: one LDS OR per lane into its slot's word, read back, cleared
-    const bool one_round = (a.ablate & kAblNoRounds) != 0;
+    const bool one_round = (RL_ABLATION(a) & kAblNoRounds) != 0;
     uint64_t peers = 1ULL << lane;
     if (!one_round) {
         if (slot >= 0) atomicOr((unsigned long long*)&S.pm[slot], 1ULL << lane);
@@ -384,7 +384,7 @@ __device__ inline Applied wave_apply(const RegionArgs& a, LdsT& S, const DevLimi
         // Token bucket, acquires only (the common group): tb_step's acquire branch in
         // straight-line code per round (Lua :56-65; elapsed as one exact integer difference,
         // times below 2^53). A round decides each key's requests up to its first allow.
-        if (!(a.ablate & kAblNoStep) && !__any(pending && q.op != (uint32_t)kOpAcquire)) {
+        if (!(RL_ABLATION(a) & kAblNoStep) && !__any(pending && q.op != (uint32_t)kOpAcquire)) {
             if (pending && (int64_t)q.permits > L.max_permits) {       // :110-116, no state access
                 r.rem = kRemUnknown;
                 pending = false;
@@ -448,7 +448,7 @@ __device__ inline Applied wave_apply(const RegionArgs& a, LdsT& S, const DevLimi
         const uint64_t kp = peers & pm;                        // my key's pending requests
         if (pending) {
             const uint64_t sa = S.sa[slot], sb = S.sb[slot], sc = S.sc[slot];
-            if (a.ablate & kAblNoStep) {
+            if (RL_ABLATION(a) & kAblNoStep) {
                 o.mutate = (q.permits & 1) != 0; o.allowed = o.mutate; o.remaining = q.permits;
                 o.a = sa; o.b = sb; o.c = sc;
             } else {
@@ -565,7 +565,7 @@ __device__ inline void region_body_t(const RegionArgs& a, uint32_t g, LdsT& S) {
     const uint32_t n_bins = a.n_regions;
     if (bin >= n_bins) return;
     if (a.hot_mark && a.hot_mark[bin] == a.epoch) return;     // owned by hot_chain
-    if (a.ablate & kAblNoNormal) return;
+    if (RL_ABLATION(a) & kAblNoNormal) return;
     const uint32_t start = a.rstart[bin];
     const uint32_t cnt = a.rend ? a.rend[bin] - start : a.rcount[bin];
     if (cnt == 0) return;
@@ -602,7 +602,7 @@ __device__ inline void region_body_t(const RegionArgs& a, uint32_t g, LdsT& S) {
         if (L.cache_table) xtab = as_global((uint64_t*)L.cache_table + (size_t)(region - L.region_base) * NS);
     // Few records: probe and update single buckets in HBM (128 B read + 32 B written per
     // distinct key) instead of moving the 8 KB image both ways.
-    const bool sparse = kSparseOn && cnt <= a.sparse_max && !(a.ablate & kAblNoProbe);
+    const bool sparse = kSparseOn && cnt <= a.sparse_max && !(RL_ABLATION(a) & kAblNoProbe);
     SparseSrc sp{sparse ? tab : nullptr, xtab, batch_min, false};
     bool tombs = false;                              // an image region kept dead slots as tombstones
     // rebuild the LDS table from registers: linear probing from each key's home

@@ -44,7 +44,7 @@ __global__ __launch_bounds__(kTileThreads) void k_unpermute(UnpermArgs a) {
   const uint32_t* __restrict__ pos1 = a.pos1;
   constexpr int B = 8;                         // rounds per batch (loads issued together)
   constexpr int NB = kTileItems / B;
-  const bool simple = pos1 || a.tokens_out || (a.ablate & kAblNoGather);
+  const bool simple = pos1 || a.tokens_out || (RL_ABLATION(a) & kAblNoGather);
   // two-pass batches: mid (res) holds the normal records' results in pass-0 order, res_hi
   // the routed records' results at their own (pass-0) positions >= n_normal
   const Res* __restrict__ res_hi = (const Res*)a.res_hi;
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(kTileThreads) void k_unpermute(UnpermArgs a) {
 #pragma unroll
             for (int k = 0; k < B; ++k) p[k] = p[k] < nn ? pos1[p[k]] : p[k];
         }
-        if (a.ablate & kAblNoGather) {
+        if (RL_ABLATION(a) & kAblNoGather) {
 #pragma unroll
             for (int k = 0; k < B; ++k) v[k] = (Res)p[k];
         } else {
@@ -244,7 +244,7 @@ hipError_t launch_unpermute(const UnpermArgs& a_in, int res_bytes, hipStream_t s
             a.res = a.mid;
             a.pos1 = nullptr;
         }
-        if (a.split && !a.pos1 && !a.tokens_out && !a.ablate)
+        if (a.split && !a.pos1 && !a.tokens_out && !RL_ABLATION(a))
             hipLaunchKernelGGL(k_unpermute_split<Res>, g, dim3(2 * kTileThreads), 0, s, a);
         else
             hipLaunchKernelGGL(k_unpermute<Res>, g, dim3(kTileThreads), 0, s, a);

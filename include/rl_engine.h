@@ -364,8 +364,9 @@ int  rl_batch_stats_get(rl_engine* e, rl_batch_stats* out);
  * names[i] are static strings. Returns the number of stages written (<= cap). */
 int  rl_stage_times(rl_engine* e, const char** names, float* ms, int cap);
 int  rl_sync(rl_engine* e);
-/* Tuning / measurement knobs (not needed by callers): "ablate" = bit set of
- * measurement-only kernel variants whose results are NOT valid (0 = product path);
+/* Tuning / measurement knobs (not needed by callers); an unknown key is RL_E_INVALID_ARG.
+ * "ablate" is no key of this library: the kernel variants that are wrong by design exist only
+ * in the measurement build (-DRL_MEASURE=1, tools/build_variant.sh), where it is their bit set.
  * "hot_threshold" (records per region for the hot-key chains, 0 = off), "route" (two-pass
  * tables: the previous batch's hot regions skip the second partition pass, default 1),
  * "region_order" (largest regions dispatched first, default 1), "walk" (the hot chains' allow

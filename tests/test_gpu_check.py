@@ -42,7 +42,9 @@ def eng():
 
 
 def new_report():
-    return torch.full((rl_amd.CHECK_WORDS,), 0x5A5A5A5A, dtype=torch.int64, device="cuda")
+    out = torch.full((rl_amd.CHECK_WORDS,), 0x5A5A5A5A, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()       # the fill runs on torch's stream, the check on the engine's
+    return out
 
 
 def fetch(e, out):

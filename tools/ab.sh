@@ -1,4 +1,6 @@
 # usage: bash tools/ab.sh "<variants>"   (GPU box) — parity tests, then interleaved variants
+# (a non-zero ablate= needs RL_ENGINE_LIB set to the measurement build, tools/build_variant.sh
+# measure "-DRL_MEASURE=1": with any other library ablate.py says so in one line and ends)
 set -o pipefail
 mkdir -p gpurun_out
 timeout -k 10 480 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > gpurun_out/gpu_tests_ab.log 2>&1; rc=$?

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Interleaved A/B timing of measurement-only kernel variants (rl_tune "ablate") in ONE
-process on the bench workload. Prints per-stage median ms for each variant."""
+"""Interleaved A/B timing of rl_tune variants in ONE process on the bench workload. Prints
+per-stage median ms for each variant. A variant with a non-zero "ablate" (kernel variants that
+are wrong by design) needs the measurement build: tools/build_variant.sh measure "-DRL_MEASURE=1",
+then RL_ENGINE_LIB=distributed-rate-limiter_amd/variants/measure/librl_engine.so."""
 import argparse
 import json
 import os
@@ -14,6 +16,7 @@ import torch  # noqa: E402
 
 import rl_amd  # noqa: E402
 from bench import CONFIGS, NS, T0_NS  # noqa: E402
+from measure_tune import tune  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--config", default="tb_uniform")
@@ -45,10 +48,10 @@ DEFAULTS = {"ablate": 0, "upsweep_per_cu": 0, "scatter_per_cu": 0,
 
 def apply(v):
     for k, x in DEFAULTS.items():          # every variant starts from the defaults
-        eng.tune(k, x)
+        tune(eng, k, x)
     for kv in v.split(","):
         k, x = kv.split("=")
-        eng.tune(k, int(x))
+        tune(eng, k, int(x))
 
 
 
@@ -64,7 +67,6 @@ for r in range(args.rounds):
         st = eng.stage_times()
         for k, ms in st.items():
             res[v].setdefault(k, []).append(ms)
-eng.tune("ablate", 0)
 out = {}
 for v in variants:
     out[v] = {k: round(statistics.median(x), 4) for k, x in res[v].items()

@@ -14,6 +14,7 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 import rl_amd  # noqa: E402
+from measure_tune import tune  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--config", default="sw_zipf")
@@ -31,7 +32,7 @@ for gb in [int(x) for x in a.bits.split(",")]:
     eng.tune("group_bits", gb)
     for kv in a.tune:
         k, v = kv.split("=")
-        eng.tune(k, int(v))
+        tune(eng, k, int(v))
     inputs = bench.make_inputs(eng, cfg, n, 1, 0, a.steps, dev)
     al = torch.empty(n, dtype=torch.uint8, device=dev)
     rem = torch.empty(n, dtype=torch.int64, device=dev)

@@ -13,6 +13,7 @@ import torch  # noqa: E402
 
 import rl_amd  # noqa: E402
 from bench import CONFIGS, T0_NS  # noqa: E402
+from measure_tune import tune  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--config", default="sw_zipf")
@@ -28,7 +29,7 @@ for l in cfg["limiters"]:
 eng.tune("debug_regions", 1)
 for kv in args.tune:
     k, v = kv.split("=")
-    eng.tune(k, int(v))
+    tune(eng, k, int(v))
 dev = torch.device("cuda", 0)
 keys = torch.empty(n, dtype=torch.int64, device=dev)
 permits = torch.empty(n, dtype=torch.int32, device=dev)

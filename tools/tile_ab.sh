@@ -1,5 +1,7 @@
 # A/B of variant builds (tools/build_variant.sh) on the bench workload; one process per variant.
 # usage: bash tools/tile_ab.sh "<variants for ablate.py>" name1 name2 ...   ("base" = the in-tree build)
+# (a non-zero ablate= needs builds made with -DRL_MEASURE=1: otherwise the run ends at that
+# variant, and the last line of its log names the measurement build and how to make it)
 set -o pipefail
 V=$1; shift
 for v in "$@"; do
