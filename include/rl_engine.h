@@ -947,8 +947,14 @@ int  rl_route_unwire(rl_engine* e, size_t m, const uint64_t* wire, uint32_t n_sr
 /* Width in bytes (1, 2, 4 or 8) of the engine's packed decision ((remaining + 3) << 1 |
  * allowed) for its current limiter set: 1 B for every maxPermits <= 124. */
 int  rl_result_width(rl_engine* e);
-/* packed[j] = (remaining[j] + 3) << 1 | allowed[j] in `width` bytes (return trip), and
- * its inverse scattered through perm: allowed[perm[j]], remaining[perm[j]]. */
+/* packed[j] = (remaining[j] + 3) << 1 | (allowed[j] & 1) in `width` bytes (return trip), and
+ * its inverse scattered through perm: allowed[perm[j]], remaining[perm[j]].
+ * These two calls have no escape mechanism: the pair is exact for remaining in
+ * [-3, ((2^(8 width) - 1) >> 1) - 3] (124 at width 1, 32764 at 2, 2^31 - 4 at 4, 2^63 - 4 at
+ * 8), which holds every reply of an engine whose rl_result_width is `width` except a
+ * token-bucket balance below -3 after time regression. A remaining outside that range is
+ * truncated to `width` bytes and comes back as another value, with no error; a caller that may
+ * see such values uses rl_route_fold_return / rl_route_unpack_return below. */
 int  rl_route_fold_packed(rl_engine* e, size_t n, const uint8_t* allowed, const int64_t* remaining,
                           void* packed, int width, void* stream);
 int  rl_route_unpack_packed(rl_engine* e, size_t n, const uint32_t* perm, const void* packed,
@@ -959,10 +965,18 @@ int  rl_route_unpack_packed(rl_engine* e, size_t n, const uint32_t* perm, const 
  * with exception block = { u64 count, exc_cap x (i64 position, i64 remaining) } listing the
  * results whose remaining does not fit the width (token-bucket balances below -3 after
  * time regression, Lua :56-58). Segment s covers requests [sum(seg_counts[<s]), +seg_counts[s]).
- * rl_route_return_bytes = total bytes of that layout (0 on bad arguments).
+ * The block's count is the segment's true number of such results, also past exc_cap; only the
+ * first exc_cap to arrive are listed, in no particular order.
+ * rl_route_return_bytes = total bytes of that layout (0 on bad arguments: n_seg 0 or > 64, a
+ * width other than 1, 2, 4, 8). A layout of n_seg segments is n_seg one-segment layouts in a
+ * row, so the total is also the sum of the one-segment totals.
  * rl_route_unpack_return scatters through perm like rl_route_unpack_packed and adds to
- * *lost (device u32) the escaped results whose block overflowed (they read
- * RL_REMAINING_ERROR). */
+ * *lost (device u32) the escaped results whose block overflowed (they read allowed 0,
+ * remaining RL_REMAINING_ERROR). An escaped result that its block lists comes back with its
+ * exact remaining and allowed = 0, whatever allowed was folded: that is right for everything an
+ * engine emits, since rl_result_width covers max_permits and so only a negative balance, which
+ * is never allowed, escapes. Both calls return RL_E_INVALID_ARG, before any device call, for a
+ * width other than 1, 2, 4, 8, n_seg 0 or > 64, or seg_counts that do not sum to m / n. */
 uint64_t rl_route_return_bytes(uint32_t n_seg, const uint64_t* seg_counts, int width,
                                uint32_t exc_cap);
 int  rl_route_fold_return(rl_engine* e, size_t m, const uint8_t* allowed, const int64_t* remaining,

@@ -8,6 +8,8 @@
 //                      engine failure on one rank, steps split into rounds (an owner receives
 //                      more than its receive capacity), and what a router reserves
 //   test_router rccl : one rank over the RCCL transport (librl_rccl.so), world 1
+//   test_router shards : the loopback cases again at the larger shard counts the header promises,
+//                      G = 8 (compact, exception blocks, split rounds), 16 (directory) and 64
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -81,6 +83,7 @@ struct Loop {
     std::mutex mu;
     std::condition_variable cv;
     int arrived = 0, gen = 0;
+    bool walk_off = false;            // every rank's engine runs without the allow-walk
     struct Post { const void* send; const uint64_t* so; const uint64_t* sb; } post[64];
     explicit Loop(int g) : G(g) {}
     void barrier() {
@@ -139,6 +142,7 @@ static void run_rank(int G, int rank, Loop* loop, const Trace* tr, size_t n, int
         uint16_t id;
         CHECK(rl_add_limiter_ex(e, &c, &id) == RL_OK && id == l);
     }
+    if (loop->walk_off) CHECK(rl_tune(e, "walk", 0) == RL_OK);   // no allow-walk tables on this engine
     LoopRank lr{loop, rank};
     rl_transport t{&lr, loop_a2av};
     if (ext_t) t = *ext_t;
@@ -190,8 +194,9 @@ static void run_rank(int G, int rank, Loop* loop, const Trace* tr, size_t n, int
     rl_destroy(e);
 }
 
-static void compare(const Trace& tr, int G, size_t n, int steps, const std::vector<Result>& res,
-                    const char* what) {
+// returns the number of remainders below -3 (the ones that travel in exception blocks)
+static size_t compare(const Trace& tr, int G, size_t n, int steps, const std::vector<Result>& res,
+                      const char* what) {
     const size_t N = tr.key.size();
     orc_state* o = orc_create();
     for (int l = 0; l < 2; ++l) orc_add_limiter(o, (int)kLims[l][0], kLims[l][1], kLims[l][2], kRefill[l]);
@@ -215,12 +220,16 @@ static void compare(const Trace& tr, int G, size_t n, int steps, const std::vect
             }
     CHECK(bad == 0);
     std::printf("%s: %zu requests, %zu mismatches, %zu out-of-range remainders\n", what, N, bad, neg);
+    return neg;
 }
 
-static void loop_case(int G, size_t n, int steps, int64_t span_ms, bool regress, bool dir,
-                      const char* what, size_t recv_cap = 0) {
+static size_t loop_case(int G, size_t n, int steps, int64_t span_ms, bool regress, bool dir,
+                        const char* what, size_t recv_cap = 0, bool walk_off = false, int split = -1) {
+    // split: whether every step must split into rounds (-1: exactly when a recv_cap is given)
+    const bool want_split = split < 0 ? recv_cap != 0 : split != 0;
     Trace tr = make_trace((size_t)G * n * steps, 0xC0FFEE + G + (regress ? 7 : 0), span_ms, regress);
     Loop loop(G);
+    loop.walk_off = walk_off;
     std::vector<Result> res(G);
     std::vector<std::thread> th;
     for (int rank = 0; rank < G; ++rank)
@@ -232,18 +241,19 @@ static void loop_case(int G, size_t n, int steps, int64_t span_ms, bool regress,
         CHECK(res[rank].finish == RL_OK);
         CHECK(res[rank].st.steps == (uint64_t)steps);
         if (dir) CHECK(res[rank].placed == 16 && res[rank].placed == res[0].placed);
-        if (recv_cap) {                          // every step split into the same rounds everywhere
+        if (recv_cap) CHECK(res[rank].st.recv_cap == recv_cap);
+        if (want_split) {                        // every step split into the same rounds everywhere
             CHECK(res[rank].st.split_steps == (uint64_t)steps);
             CHECK(res[rank].st.rounds == res[0].st.rounds && res[rank].st.rounds > (uint64_t)steps);
-            CHECK(res[rank].st.recv_cap == recv_cap);
         } else {
             CHECK(res[rank].st.split_steps == 0 && res[rank].st.rounds == (uint64_t)steps);
         }
     }
-    compare(tr, G, n, steps, res, what);
+    const size_t neg = compare(tr, G, n, steps, res, what);
     std::printf("  rounds %llu over %d steps, max received %llu, header sync %.3f ms/step\n",
                 (unsigned long long)res[0].st.rounds, steps, (unsigned long long)res[0].st.max_recv,
                 res[0].st.header_sync_ns * 1e-6 / steps);
+    return neg;
 }
 
 // One rank's engine fails a batch (fail_batches, before anything is enqueued): that rank's
@@ -442,6 +452,21 @@ int main(int argc, char** argv) {
         loop_span_case();
         loop_error_case();
         loop_empty_rounds_case();
+    } else if (mode == "shards") {
+        // Shard counts past 4: owner ballots of 3, 4 and 6 bits, header rows with 8, 16 and 64
+        // count words in use, return layouts and wire sources of as many segments. Every case
+        // runs 3 steps, because a status is published two steps back.
+        loop_case(8, 10000, 3, 30000, false, false, "G=8 compact");
+        CHECK(loop_case(8, 10000, 3, 30000, true, false, "G=8 TB regression (exception blocks)") > 0);
+        loop_case(8, 10000, 3, 30000, false, false, "G=8 split rounds (recv_cap 4000)", 4000);
+        // The trace's hottest key draws 8 % of all requests: 1.3 n at G = 16 and 5.4 n at G = 64
+        // reach one owner for it alone, past the default receive capacity of 2 n. These two
+        // cases give every owner room for a whole step (G n), so each step is one round.
+        loop_case(16, 5000, 3, 30000, false, true, "G=16 hot-key directory", 16 * 5000, false, 0);
+        // 64 engines in one process: an engine allocates its 512 MiB allow-walk tables the first
+        // time a batch has a key dense enough to walk, and this skewed trace has such keys, so
+        // the walk is switched off on these engines (it is optional and decides identically).
+        loop_case(64, 1024, 3, 30000, false, false, "G=64 compact", 64 * 1024, true, 0);
     } else if (mode == "rccl") {
         char id[RL_RCCL_ID_BYTES];
         CHECK(rl_rccl_unique_id(id) == RL_OK);

@@ -13,6 +13,8 @@
 //   test_router_query retry    : the queries again with a small recv_cap, the wide layout, the
 //                                directory, and without limiter ids
 //   test_router_query mismatch : routers with different max_batch
+//   test_router_query shards   : G = 8, operations and queries in split rounds, with and without
+//                                the directory
 // Every case runs 3 steps, 3 query calls per rank (the last step's own arrays with
 // skip = allowed; crafted queries; a layout with one empty rank and one rank all skipped), a
 // 4th step and rl_router_finish. A counting wrapper around the transport checks the number of
@@ -525,7 +527,14 @@ int main(int argc, char** argv) {
                          {"G=4 queries, wide + recv_cap 7000", 4, 7000, true, false, false, false},
                          {"G=4 queries, directory + recv_cap 7000", 4, 7000, false, true, false, false},
                          {"G=2 queries without limiter ids", 2, 0, false, false, true, false}};
-    if (mode == "execute") {
+    // G = 8: the Zipf-1.2 trace's first key draws a fifth of all requests, 1.7 n of the 8 n of a
+    // step, so its owner receives more than the default capacity of 2 n: both cases state a
+    // receive capacity and every step runs in rounds
+    const Cfg shards[] = {{"G=8 ops, split rounds (recv_cap 7000)", 8, 7000, false, false, false, false},
+                          {"G=8 queries, directory + recv_cap 7000", 8, 7000, false, true, false, false}};
+    if (mode == "shards") {
+        for (const Cfg& c : shards) run_case(c);
+    } else if (mode == "execute") {
         for (const Cfg& c : exec) run_case(c);
     } else if (mode == "retry") {
         for (const Cfg& c : retry) run_case(c);

@@ -57,7 +57,7 @@ def _owners(keys, shards, dir_keys, dir_owner):
     return own
 
 
-@pytest.mark.parametrize("shards", [1, 2, 8])
+@pytest.mark.parametrize("shards", [1, 2, 4, 8, 16, 32, 64])
 @pytest.mark.parametrize("n", SIZES)
 def test_skip_partition(n, shards):
     eng, dk, do = _engine(shards)

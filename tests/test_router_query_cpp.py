@@ -1,5 +1,5 @@
 """Mixed operations and retry-after queries through the C-ABI router (rl_router_execute,
-rl_router_retry_after) driven from C++ (tests/cpp/test_router_query.cpp): G = 2 / 4 routers as
+rl_router_retry_after) driven from C++ (tests/cpp/test_router_query.cpp): G = 2 / 4 / 8 routers as
 threads on the box's GPU over the in-process transport, every decision and every wait equal to
 one unsharded engine's on the concatenated stream; one subprocess per mode."""
 import os
@@ -29,6 +29,11 @@ def test_execute_with_ops_equals_one_engine():
 def test_retry_after_equals_one_engine_in_every_exchange_mode():
     out = _run("retry")
     assert out.count(" 0 mismatches") == 4 and out.count(" 0 wait mismatches") == 4, out
+
+
+def test_execute_and_retry_after_at_eight_shards():
+    out = _run("shards")
+    assert out.count(" 0 mismatches") == 2 and out.count(" 0 wait mismatches") == 2, out
 
 
 def test_capacity_mismatch_fails_every_rank():
