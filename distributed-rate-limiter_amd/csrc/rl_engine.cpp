@@ -170,6 +170,7 @@ extern "C" void rl_destroy(rl_engine* e) {
     for (auto& l : e->lims) { dfree(l.table); dfree(l.cache_table); }
     for (auto& pb : e->pinned) (void)hipHostUnregister(pb.first);
     if (e->h_ctl) (void)hipHostFree(e->h_ctl);
+    if (e->sm_block) (void)hipHostFree(e->sm_block);
     for (BatchScratch& B : e->sc) {
         if (B.parted) (void)hipEventDestroy(B.parted);
         if (B.freed) (void)hipEventDestroy(B.freed);
@@ -518,6 +519,11 @@ extern "C" int rl_tune(rl_engine* e, const char* key, int64_t value) {
         e->epoch = (uint32_t)value;
         return RL_OK;
     }
+    if (std::strcmp(key, "small_batch") == 0) {       // batches up to `value` requests ask for the small path; 0 = off
+        if (value < 0) return RL_E_INVALID_ARG;
+        e->small_batch = (uint64_t)value;
+        return RL_OK;
+    }
     if (std::strcmp(key, "fail_batches") == 0) {      // the next `value` batches fail (RL_E_DEVICE)
         if (value < 0 || value > 0xFFFFFFFFLL) return RL_E_INVALID_ARG;
         e->inject_fail = (uint32_t)value;
@@ -531,7 +537,7 @@ extern "C" int rl_sync(rl_engine* e) {
     std::lock_guard<std::mutex> lk(e->mu);
     HIP_OK(hipStreamSynchronize(e->stream));
     if (e->pstream) HIP_OK(hipStreamSynchronize(e->pstream));
-    if (e->pending_status) {                                 // the last batch is complete
+    if (e->pending_status && !e->last_small) {               // the last batch is complete
         e->hot_hint = e->h_ctl->n_hot;
         e->walk_hint = e->h_ctl->n_walk;
     }

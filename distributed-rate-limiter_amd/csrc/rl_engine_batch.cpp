@@ -1,7 +1,10 @@
 // rl_engine_batch.cpp — a batch: its scratch, the launch chain (run_batch_device), the status
 // it leaves behind, and the calls that run one (rl_execute_batch(_device), peek and reset).
-// The arithmetic of a batch is rl_batch_plan.hpp.
+// The arithmetic of a batch is rl_batch_plan.hpp. A batch of at most rl_tune("small_batch")
+// requests takes one launch instead of the chain (small_route, run_small, run_small_host; the
+// kernel: rl_small.hip).
 #include "rl_engine_impl.hpp"
+#include "rl_small.hpp"
 
 using namespace rl;
 
@@ -68,20 +71,87 @@ static inline void mark_on(rl_engine* e, hipStream_t st, int i) {
 }
 static inline void mark(rl_engine* e, int i) { mark_on(e, e->stream, i); }
 
+// ------------------------------------------------------------------ the small-batch path
+// Who asks: a caller of the public entry points, the router for a batch of its own, the
+// string-key call; `decided`: the host form chose before it staged anything.
+enum class SmallAsk { decided, caller, router, keys };
+static_assert(kSmallMax == RL_SMALL_BATCH_MAX, "rl_small.hpp and rl_engine.h agree");
+
+// Whether this batch takes the path. A batch of eligible size (n <= rl_tune "small_batch")
+// that does not is counted as declined; the reasons are the list of include/rl_engine.h.
+static bool small_route(rl_engine* e, size_t n, SmallAsk who) {
+    if (e->small_batch == 0 || n == 0 || n > e->small_batch) return false;
+    bool wide = e->force_wide;
+    for (auto& l : e->lims) wide |= l.cfg.max_permits > kCompactMaxPermits;
+    if (n > kSmallMax || who != SmallAsk::caller || e->timing || e->pipeline || e->debug_regions ||
+        e->lims.empty() || wide) {
+        ++e->small_declined;
+        return false;
+    }
+    return true;
+}
+
+static int ensure_small(rl_engine* e) {
+    int rc = e->sm_rec.reserve(small_rec_count());
+    if (rc == RL_OK) rc = e->sm_res.reserve(small_rec_count());
+    if (rc == RL_OK) rc = e->sm_ext.reserve(small_rec_count());
+    if (rc == RL_OK) rc = e->sm_tok.reserve(small_rec_count());
+    if (rc == RL_OK) rc = e->sm_ctl.reserve(1);
+    if (rc == RL_OK) rc = e->sm_stats.reserve(kStWords);
+    // (indexed by region: they follow the tables' growth; growing frees, which waits for the device)
+    if (rc == RL_OK) rc = e->sm_rstart.reserve(small_region_words(e->n_regions));
+    if (rc == RL_OK) rc = e->sm_rend.reserve(small_region_words(e->n_regions));
+    if (rc == RL_OK) rc = e->sm_order.reserve(small_order_words(e->n_regions));
+    return rc;
+}
+
+// One launch on e->stream: the whole batch, its control block into h_ctl (mapped) by the kernel
+// itself. The arrays are the caller's device arrays, or the host form's mapped block.
+static int run_small(rl_engine* e, size_t n, const uint64_t* key, const int32_t* permits,
+                     const int64_t* now_ns, const uint16_t* limiter, const uint8_t* op,
+                     uint8_t* allowed, int64_t* remaining, double* tokens_after) {
+    const int rc = ensure_small(e);
+    if (rc != RL_OK) return rc;
+    SmallArgs a{};
+    RegionArgs& ra = a.ra;
+    ra.rec = e->sm_rec; ra.rstart = e->sm_rstart; ra.rend = e->sm_rend;
+    ra.region_lim = e->d_region_lim; ra.lims = e->d_lims;
+    ra.res = e->sm_res; ra.ext = e->sm_ext; ra.tok = e->sm_tok; ra.ctl = e->sm_ctl;
+    ra.n_regions = e->n_regions; ra.n_total = (uint32_t)n; ra.shard_bits = e->shard_bits;
+    ra.skew_ms = e->opts.max_skew_ms; ra.stats = e->sm_stats;
+    for (auto& l : e->lims) ra.cache |= l.dev.cache_ttl_ms > 0 ? 1u : 0u;
+    ra.sparse_max = e->sparse_max;
+    ra.order = e->sm_order; ra.order_prefix = 0;
+    a.key = key; a.permits = permits; a.now_ns = now_ns; a.limiter = limiter; a.op = op;
+    a.allowed = allowed; a.remaining = remaining; a.tokens_out = tokens_after;
+    a.rstart = e->sm_rstart; a.rend = e->sm_rend; a.order = e->sm_order;
+    HIP_OK(hipHostGetDevicePointer((void**)&a.ctl_out, e->h_ctl, 0));
+    a.n = (uint32_t)n; a.n_lim = (uint32_t)e->lims.size();
+    e->last_wide = false;
+    HIP_OK(launch_small_batch(a, e->stream));
+    ++e->small_taken;
+    e->last_small = true;
+    e->pending_status = true;
+    return RL_OK;
+}
+
 // The pipeline on device buffers, enqueued on e->stream. Returns an immediate status
 // (argument/launch errors); the data-dependent status is read back by rl_last_status.
 static int run_batch_device(rl_engine* e, size_t n, const uint64_t* key, const int32_t* permits,
                             const int64_t* now_ns, const uint16_t* limiter, const uint8_t* op,
                             uint8_t* allowed, int64_t* remaining, double* tokens_after,
-                            bool overlap = false) {
+                            bool overlap = false, SmallAsk small = SmallAsk::decided) {
     if (n > e->opts.max_batch) return RL_E_TOO_LARGE;
     e->last_n = n;
     e->pending_status = false;
     e->enqueued = false;
+    e->last_small = false;
     e->last_status = RL_OK;
     if (n == 0) return RL_OK;
     if (!key || !permits || !now_ns || !allowed || !remaining) return RL_E_INVALID_ARG;
     if (e->inject_fail) { --e->inject_fail; return RL_E_DEVICE; }   // nothing enqueued
+    if (small != SmallAsk::decided && small_route(e, n, small))
+        return run_small(e, n, key, permits, now_ns, limiter, op, allowed, remaining, tokens_after);
     hipStream_t s = e->stream;
     if (e->lims.empty()) {
         HIP_OK(launch_fill_invalid(allowed, remaining, tokens_after, (uint32_t)n, s));
@@ -349,8 +419,10 @@ int collect_status(rl_engine* e) {
     if (!e->pending_status) return e->last_status;
     e->pending_status = false;
     BatchCtl& c = *e->h_ctl;
-    e->hot_hint = c.n_hot;
-    e->walk_hint = c.n_walk;
+    if (!e->last_small) {                            // (a small batch says nothing about hot regions)
+        e->hot_hint = c.n_hot;
+        e->walk_hint = c.n_walk;
+    }
     const int st = status_of(c.invalid != 0, c.cap_err != 0, c.span_overflow != 0, c.internal_err != 0);
     e->last_status = st;
     apply_growth(e, c.grow, c.cap_err != 0);
@@ -388,21 +460,49 @@ int engine_status_settle(rl_engine* e, const unsigned long long* acc) {
 }
 }  // namespace rl
 
-extern "C" int rl_execute_batch_device(rl_engine* e, size_t n, const uint64_t* key,
-                                       const int32_t* permits, const int64_t* now_ns,
-                                       const uint16_t* limiter, const uint8_t* op,
-                                       uint8_t* allowed, int64_t* remaining, double* tokens_after,
-                                       void* stream) {
+static int execute_device(rl_engine* e, size_t n, const uint64_t* key, const int32_t* permits,
+                          const int64_t* now_ns, const uint16_t* limiter, const uint8_t* op,
+                          uint8_t* allowed, int64_t* remaining, double* tokens_after, void* stream,
+                          SmallAsk who) {
     if (!e) return RL_E_INVALID_ARG;
     std::lock_guard<std::mutex> lk(e->mu);
     (void)hipSetDevice(e->device);
     StreamJoin join(e->stream, (hipStream_t)stream);
     HIP_OK(join.err);
     const int rc = run_batch_device(e, n, key, permits, now_ns, limiter, op, allowed, remaining,
-                                    tokens_after, /*overlap=*/stream == nullptr);
+                                    tokens_after, /*overlap=*/stream == nullptr, who);
     HIP_OK(join.finish());
     return rc;
 }
+
+extern "C" int rl_execute_batch_device(rl_engine* e, size_t n, const uint64_t* key,
+                                       const int32_t* permits, const int64_t* now_ns,
+                                       const uint16_t* limiter, const uint8_t* op,
+                                       uint8_t* allowed, int64_t* remaining, double* tokens_after,
+                                       void* stream) {
+    return execute_device(e, n, key, permits, now_ns, limiter, op, allowed, remaining, tokens_after,
+                          stream, SmallAsk::caller);
+}
+
+namespace rl {
+int engine_execute_routed(rl_engine* e, size_t n, const uint64_t* key, const int32_t* permits,
+                          const int64_t* now_ns, const uint16_t* limiter, const uint8_t* op,
+                          uint8_t* allowed, int64_t* remaining, double* tokens_after, void* stream) {
+    return execute_device(e, n, key, permits, now_ns, limiter, op, allowed, remaining, tokens_after,
+                          stream, SmallAsk::router);
+}
+}  // namespace rl
+
+extern "C" int rl_small_batches(rl_engine* e, uint64_t* taken, uint64_t* declined) {
+    if (!e) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (taken) *taken = e->small_taken;
+    if (declined) *declined = e->small_declined;
+    return RL_OK;
+}
+
+// The string-key call stages and hashes on the device: always the pipeline (counted as declined).
+void small_decline_keys(rl_engine* e, size_t n) { (void)small_route(e, n, SmallAsk::keys); }
 
 extern "C" int rl_last_status(rl_engine* e) {
     if (!e) return RL_E_INVALID_ARG;
@@ -466,6 +566,53 @@ int run_staged_batch(rl_engine* e, size_t n, bool limiter, bool op, uint8_t* all
     return rc;
 }
 
+// The host form of the small-batch path: the requests packed into the engine's page-locked
+// block, which the kernel reads and writes in place (mapped), one synchronisation, the results
+// copied out. A batch whose span the compact records cannot hold was rejected before any state
+// was touched: it goes to the pipeline in 32-B records, as run_staged_batch's retry does.
+static int run_small_host(rl_engine* e, size_t n, const uint64_t* key, const int32_t* permits,
+                          const int64_t* now_ns, const uint16_t* limiter, const uint8_t* op,
+                          uint8_t* allowed, int64_t* remaining, double* tokens_after) {
+    e->last_n = n;
+    e->pending_status = false;
+    e->enqueued = false;
+    e->last_small = false;
+    e->last_status = RL_OK;
+    if (e->inject_fail) { --e->inject_fail; return RL_E_DEVICE; }
+    const SmallBlock b = small_block();
+    if (!e->sm_block && hipHostMalloc((void**)&e->sm_block, b.bytes) != hipSuccess) {
+        e->sm_block = nullptr;
+        return RL_E_NOMEM;
+    }
+    uint8_t* h = e->sm_block;
+    uint8_t* d = nullptr;
+    HIP_OK(hipHostGetDevicePointer((void**)&d, h, 0));
+    std::memcpy(h + b.key, key, n * 8);
+    std::memcpy(h + b.now_ns, now_ns, n * 8);
+    std::memcpy(h + b.permits, permits, n * 4);
+    if (limiter) std::memcpy(h + b.limiter, limiter, n * 2);
+    if (op) std::memcpy(h + b.op, op, n);
+    int rc = run_small(e, n, (const uint64_t*)(d + b.key), (const int32_t*)(d + b.permits),
+                       (const int64_t*)(d + b.now_ns), limiter ? (const uint16_t*)(d + b.limiter) : nullptr,
+                       op ? d + b.op : nullptr, d + b.allowed, (int64_t*)(d + b.remaining),
+                       tokens_after ? (double*)(d + b.tokens) : nullptr);
+    if (rc != RL_OK) { (void)hipStreamSynchronize(e->stream); return rc; }
+    rc = collect_status(e);
+    if (rc == RL_E_INVALID_ARG && e->h_ctl->span_overflow) {
+        ++e->small_declined;                          // (wide records: the pipeline's)
+        e->force_wide = true;                         // (small_route declined a force_wide engine)
+        rc = stage_requests(e, n, key, permits, now_ns, limiter, op);
+        if (rc == RL_OK)
+            rc = run_staged_batch(e, n, limiter != nullptr, op != nullptr, allowed, remaining, tokens_after);
+        e->force_wide = false;
+        return rc;
+    }
+    std::memcpy(allowed, h + b.allowed, n);
+    std::memcpy(remaining, h + b.remaining, n * 8);
+    if (tokens_after) std::memcpy(tokens_after, h + b.tokens, n * 8);
+    return rc;
+}
+
 extern "C" int rl_execute_batch(rl_engine* e, size_t n, const uint64_t* key,
                                 const int32_t* permits, const int64_t* now_ns,
                                 const uint16_t* limiter, const uint8_t* op, uint8_t* allowed,
@@ -476,6 +623,8 @@ extern "C" int rl_execute_batch(rl_engine* e, size_t n, const uint64_t* key,
     if (n == 0) return RL_OK;
     if (!key || !permits || !now_ns || !allowed || !remaining) return RL_E_INVALID_ARG;
     (void)hipSetDevice(e->device);
+    if (small_route(e, n, SmallAsk::caller))
+        return run_small_host(e, n, key, permits, now_ns, limiter, op, allowed, remaining, tokens_after);
     int rc = stage_requests(e, n, key, permits, now_ns, limiter, op);
     if (rc != RL_OK) return rc;
     return run_staged_batch(e, n, limiter != nullptr, op != nullptr, allowed, remaining, tokens_after);

@@ -249,6 +249,19 @@ struct rl_engine {
     DevArray<uint64_t> ks_hash;             // [keys] rl_hash_keys' hashes
     DevArray<unsigned long long> ks_hdr;    // [2] the chunks' headers (the host checked the offsets)
     bool keys_direct = false;               // rl_tune("keys_direct"): k_hash_keys' direct path only
+    // the small-batch path (rl_small.hpp, run_small in rl_engine_batch.cpp), on first use
+    uint64_t small_batch = 0;               // rl_tune("small_batch"): batches up to this size ask for it; 0 = off
+    uint64_t small_taken = 0, small_declined = 0;   // rl_small_batches
+    bool last_small = false;                // the last batch ran on the path: its ctl carries no hot / walk hint
+    DevArray<rl::RecC> sm_rec;              // [small_rec_count()] records in region order
+    DevArray<uint32_t> sm_res;              // [small_rec_count()] packed results
+    DevArray<int64_t> sm_ext;               // [small_rec_count()] escaped remainders
+    DevArray<double> sm_tok;                // [small_rec_count()] balances
+    DevArray<uint32_t> sm_rstart, sm_rend;  // [n_regions] the touched regions' runs
+    DevArray<uint32_t> sm_order;            // [n_regions + 1] the touched list, its length last
+    DevArray<rl::BatchCtl> sm_ctl;          // the path's control block
+    DevArray<unsigned long long> sm_stats;  // [kStWords] the one workgroup's counters
+    uint8_t* sm_block = nullptr;            // page-locked, mapped: the host form's requests and results (small_block)
 };
 
 // rl_engine.cpp
@@ -261,5 +274,6 @@ int stage_requests(rl_engine* e, size_t n, const uint64_t* key, const int32_t* p
                    const int64_t* now_ns, const uint16_t* limiter, const uint8_t* op_or_skip);
 int run_staged_batch(rl_engine* e, size_t n, bool limiter, bool op, uint8_t* allowed,
                      int64_t* remaining, double* tokens_after);
+void small_decline_keys(rl_engine* e, size_t n);   // rl_small_batches' `declined`, for rl_execute_batch_keys
 
 #pragma GCC visibility pop

@@ -566,6 +566,7 @@ extern "C" int rl_execute_batch_keys(rl_engine* e, size_t n, const uint8_t* key_
         at += m;
     }
     if (key_hash_out) HIP_OK(hipMemcpyAsync(key_hash_out, e->s_key, n * 8, hipMemcpyDeviceToHost, s));
+    small_decline_keys(e, n);                          // (the keys are hashed into the staging arrays)
     return run_staged_batch(e, n, limiter != nullptr, op != nullptr, allowed, remaining, tokens_after);
 }
 

@@ -509,6 +509,29 @@ hipError_t launch_route_next(const HotInfo* hot_info, const uint32_t* hot_count,
 hipError_t launch_unpermute(const UnpermArgs& a, int res_bytes, hipStream_t s);
 hipError_t launch_fill_invalid(uint8_t* allowed, int64_t* remaining, double* tok, uint32_t n,
                                hipStream_t s);
+// The small-batch path (rl_small.hip; the partition and its sizes: rl_small.hpp): one workgroup
+// decides a batch of at most kSmallMax requests. `ra` is the region stage's argument block over
+// the path's own scratch (rec, rstart, rend, order with order_prefix 0, res as uint32, ext, tok,
+// ctl, stats of kStWords words; no hot marks, no route list); rstart / rend / order are the same
+// arrays, writable. The request and result arrays may be device memory or mapped host memory.
+struct SmallArgs {
+    RegionArgs ra;
+    const uint64_t* key;
+    const int32_t* permits;
+    const int64_t* now_ns;
+    const uint16_t* limiter;   // nullable
+    const uint8_t* op;         // nullable
+    uint8_t* allowed;
+    int64_t* remaining;
+    double* tokens_out;        // nullable
+    uint32_t* rstart;          // [n_regions]
+    uint32_t* rend;            // [n_regions]
+    uint32_t* order;           // [n_regions + 1]
+    BatchCtl* ctl_out;         // the finished control block once more (the host's mapped copy)
+    uint32_t n;                // 1 .. kSmallMax
+    uint32_t n_lim;
+};
+hipError_t launch_small_batch(const SmallArgs& a, hipStream_t s);
 hipError_t launch_synth(const SynthArgs& a, hipStream_t s);
 // Retry-after queries (rl_retry.hip): a read-only gather over the state tables, one answer per
 // query (wait_ms >= 0, kRetryNever, kRetryInvalid); no batch scratch, no statistics.
@@ -803,6 +826,11 @@ size_t engine_directory(rl_engine* e, uint64_t* keys, uint32_t* owners);
 // batch), and later settle the folded status of several batches at a step boundary: the
 // status those batches return together, with the table growth they asked for applied once.
 int engine_status_accum(rl_engine* e, unsigned long long* acc, void* stream);
+// rl_execute_batch_device for the router's own batches: always the pipeline, whose d_ctl
+// engine_status_accum folds (a batch of small-batch size counts as declined, rl_small_batches).
+int engine_execute_routed(rl_engine* e, size_t n, const uint64_t* key, const int32_t* permits,
+                          const int64_t* now_ns, const uint16_t* limiter, const uint8_t* op,
+                          uint8_t* allowed, int64_t* remaining, double* tokens_after, void* stream);
 int engine_status_settle(rl_engine* e, const unsigned long long* acc_host);
 // Every device allocation of the engine units and the router (dalloc, DevArray::reserve, the
 // router's buffers): hipMalloc, then filled with rl_debug_alloc_fill's byte while that is on.

@@ -12,7 +12,7 @@
 //      more than its receive capacity — several rounds, each moving the next piece of every
 //      owner's incoming stream (sources in rank order, so per-key arrival order holds)
 //   3. payload all-to-all (+ the u16 limiter ids when there are several limiters)
-//   4. the owner's engine decides (rl_execute_batch_device)
+//   4. the owner's engine decides (engine_execute_routed: rl_execute_batch_device, always the pipeline)
 //   5. decisions back in the engine's packed width, one segment + exception block per
 //      source (exact remainders outside the width: TB balances below -3)
 //   6. scatter back to the caller's order through the partition permutation
@@ -333,7 +333,7 @@ extern "C" int rl_router_execute(rl_router* r, size_t n, const uint64_t* key, co
         // what the engine's compact records hold (+-2^31 ms around its first request) it runs
         // in full-width records (skewed clocks across front-ends).
         if (far) (void)rl_tune(e, "wide_records", 1);
-        const int xrc = rl_execute_batch_device(e, m, r->k_r, r->p_r, r->t_r, col ? r->lim_r : nullptr,
+        const int xrc = engine_execute_routed(e, m, r->k_r, r->p_r, r->t_r, col ? r->lim_r : nullptr,
                                                 op ? r->op_r : nullptr, r->a_r, r->rem_r, nullptr, s);
         if (far) (void)rl_tune(e, "wide_records", 0);
         if (xrc != RL_OK) {
@@ -382,7 +382,7 @@ extern "C" int rl_router_execute(rl_router* r, size_t n, const uint64_t* key, co
             if (op) R_RC(rl_route_unfold_ops(e, mk, r->lim_r, r->lim_r, r->op_r, s));
             const bool w = wide || far;
             if (w) (void)rl_tune(e, "wide_records", 1);
-            const int xrc = rl_execute_batch_device(e, mk, r->k_r, r->p_r, r->t_r,
+            const int xrc = engine_execute_routed(e, mk, r->k_r, r->p_r, r->t_r,
                                                     col ? r->lim_r : nullptr, op ? r->op_r : nullptr,
                                                     r->a_r, r->rem_r, nullptr, s);
             if (w) (void)rl_tune(e, "wide_records", 0);

@@ -63,6 +63,18 @@ int GpuEngine::executeBatch(size_t n, const uint64_t* key, const int32_t* permit
     return st;
 }
 
+int GpuEngine::setSmallBatch(uint64_t n) {
+    std::lock_guard<std::mutex> lk(mu_);
+    return rl_tune(e_, "small_batch", (int64_t)std::min<uint64_t>(n, (uint64_t)INT64_MAX));
+}
+
+std::pair<uint64_t, uint64_t> GpuEngine::smallBatches() {
+    std::lock_guard<std::mutex> lk(mu_);
+    uint64_t taken = 0, declined = 0;
+    (void)rl_small_batches(e_, &taken, &declined);
+    return {taken, declined};
+}
+
 int GpuEngine::executeBatchKeys(const KeyBatch& keys, const int32_t* permits, const int64_t* now,
                                 const uint16_t* limiter, const uint8_t* op, uint8_t* allowed,
                                 int64_t* remaining, uint64_t* keyHashOut, uint64_t* cacheHits) {
@@ -334,7 +346,8 @@ size_t GpuEngine::snapshotChanged(uint16_t limiter, int64_t nowNanos, uint32_t b
 }
 
 GpuRateLimiter::GpuRateLimiter(std::shared_ptr<GpuEngine> engine, Algorithm algo,
-                               const RateLimitConfig& cfg, Clock clock, int batchWindowMicros)
+                               const RateLimitConfig& cfg, Clock clock, int batchWindowMicros,
+                               uint64_t smallBatch)
     : allowedRequests(algo == Algorithm::TokenBucket ? "ratelimiter.tokenbucket.allowed"
                                                       : "ratelimiter.requests.allowed"),
       rejectedRequests(algo == Algorithm::TokenBucket ? "ratelimiter.tokenbucket.rejected"
@@ -346,6 +359,7 @@ GpuRateLimiter::GpuRateLimiter(std::shared_ptr<GpuEngine> engine, Algorithm algo
         throw IllegalArgumentException(                // TokenBucketRateLimiter.java:77-79
             "Token bucket requires positive refillRate. Use RateLimitConfig.builder().refillRate(...)");
     id_ = engine_->addLimiter((int)algo, cfg_);
+    if (smallBatch > 0) checkStatus(engine_->setSmallBatch(smallBatch), "setSmallBatch");
 }
 
 GpuRateLimiter::~GpuRateLimiter() { unpinFlush(); }

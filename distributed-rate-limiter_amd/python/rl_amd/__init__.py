@@ -56,6 +56,7 @@ OPT_FIXED_CAPACITY = 4  # RL_OPT_FIXED_CAPACITY: no on-demand table growth
 REGION_SLOTS = 256          # kRegionSlots in csrc/rl_device.hpp (state slots per region)
 MIN_REGIONS = 8             # kRegionsPerBin: every limiter has at least one bin of regions
 DIST_UNIFORM, DIST_ZIPF = 0, 1
+SMALL_BATCH_MAX = 1024      # RL_SMALL_BATCH_MAX
 
 EXPORTS = [
     "rl_create", "rl_destroy", "rl_add_limiter", "rl_add_limiter_ex", "rl_try_acquire_batch",
@@ -83,7 +84,7 @@ EXPORTS = [
     "rl_key_hash", "rl_hash_keys", "rl_hash_keys_device", "rl_execute_batch_keys",
     "rl_tally_batch", "rl_tally_batch_device", "rl_top_denied", "rl_top_denied_device",
     "rl_check_limiter", "rl_check_limiter_device", "rl_check_table_device", "rl_check_images",
-    "rl_check_images_device", "rl_debug_alloc_fill",
+    "rl_check_images_device", "rl_debug_alloc_fill", "rl_small_batches",
 ]
 RCCL_EXPORTS = ["rl_rccl_unique_id", "rl_transport_rccl_create", "rl_transport_rccl_destroy"]
 STATE_SW_BUCKET, STATE_TB_BUCKET = 0, 1
@@ -250,6 +251,8 @@ def lib():
                                  ctypes.POINTER(ctypes.c_float), ctypes.c_int]
     L.rl_sync.argtypes = [vp]
     L.rl_tune.argtypes = [vp, ctypes.c_char_p, i64]
+    if hasattr(L, "rl_small_batches"):               # (an A/B build of an older revision has none)
+        L.rl_small_batches.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.rl_strerror.argtypes = [ctypes.c_int]
     L.rl_strerror.restype = ctypes.c_char_p
     L.rl_owner_of.argtypes = [ctypes.c_uint64, u16, u32]
@@ -610,6 +613,14 @@ class Engine:
 
     def last_status(self) -> int:
         return self._L.rl_last_status(self._h)
+
+    def small_batches(self):
+        """rl_small_batches: (taken, declined) of the small-batch path (tune("small_batch", v))."""
+        taken, declined = ctypes.c_uint64(), ctypes.c_uint64()
+        st = self._L.rl_small_batches(self._h, ctypes.byref(taken), ctypes.byref(declined))
+        if st != RL_OK:
+            raise RlError(st, "rl_small_batches")
+        return taken.value, declined.value
 
     def available(self, limiter, keys, now_ns):
         keys = np.ascontiguousarray(keys, np.uint64)

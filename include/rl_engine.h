@@ -384,6 +384,48 @@ int  rl_sync(rl_engine* e);
  * counter restarts at 0 whenever the marks are (re)allocated (the first hot batch, the first
  * one after the region count grew), so set it after a hot batch on the table in question. */
 int  rl_tune(rl_engine* e, const char* key, int64_t value);
+/* ---- small batches: one launch, one round trip ----
+ * rl_tune(e, "small_batch", v), v > 0: a batch of n <= min(v, RL_SMALL_BATCH_MAX) requests given
+ * to rl_execute_batch_device (any stream), rl_execute_batch or rl_try_acquire_batch (and so
+ * rl_available and rl_reset) is decided by one kernel launch of one workgroup instead of the
+ * pipeline's chain of kernels. The host forms pack the requests into a page-locked block of the
+ * engine (allocated by the first such call, sized for RL_SMALL_BATCH_MAX), which the kernel
+ * reads and writes in place: one launch and one synchronisation, no copy enqueued. v = 0 (the
+ * default) turns the path off; v < 0 is RL_E_INVALID_ARG. Measured (DESIGN.md §4 "Small
+ * batches"): one request 33 us instead of 305 us per host call, the path ahead up to n = 256 and
+ * behind at 1024 with all-distinct keys, so v = 256 is the value to use. Its scratch (39 KiB
+ * and 12 bytes per table region) is allocated by the first batch that takes it and freed by
+ * rl_destroy.
+ *
+ * Identical to the pipeline, bit for bit: allowed, remaining, tokens_after, the returned status
+ * and rl_last_status, the limiter state left behind (rl_limiter_digest), table growth and
+ * RL_E_CAPACITY, the rejection of a batch that spans more than 2^32 ms (the host forms run it
+ * again in 32-byte records on the pipeline, as they always did), entries past n untouched, and
+ * rl_batch_stats except two fields that describe the pipeline's own work: hot_regions and
+ * routed are 0 after a small batch (no hot chains, no routing: a batch this small is far below
+ * their thresholds). The per-key order contract holds: requests of one key in array order.
+ * The path leaves the pipeline's hot marks, route list and launch hints as they were.
+ *
+ * Declined: a batch of eligible size (n <= v) that goes to the pipeline all the same, each
+ * counted once in `declined`:
+ *  - n > RL_SMALL_BATCH_MAX;
+ *  - a router's own batches (rl_router_*: their status is folded from the pipeline's control
+ *    block on the device);
+ *  - rl_execute_batch_keys (the keys are hashed into the pipeline's staging arrays);
+ *  - an engine with RL_OPT_STAGE_TIMING or rl_tune "stage_timing" / "debug_regions" on (the
+ *    stamps belong to the pipeline's stages);
+ *  - an RL_OPT_PIPELINE engine (the batch would have to be ordered behind the partition
+ *    stream's batch in flight; it is declined instead, never reordered);
+ *  - 32-byte records: a limiter with max_permits above 4194302, rl_tune "wide_records", and
+ *    the second run of a host-form batch that spans more than 2^32 ms (that batch counts once
+ *    as taken, for the run that rejected it, and once as declined);
+ *  - an engine with no limiter (the pipeline's all-invalid fill answers it).
+ * A batch of n > v, and every batch while v = 0, is not counted.
+ *
+ * rl_small_batches: `taken` = batches decided on the path, `declined` as above, both since
+ * rl_create; either pointer may be null. */
+#define RL_SMALL_BATCH_MAX 1024
+int  rl_small_batches(rl_engine* e, uint64_t* taken, uint64_t* declined);
 /* Diagnostics (not needed by callers). "region_times": after a batch run with
  * rl_tune("debug_regions", 1), copies per-bin {t_start, t_end, records, rounds, cycle
  * counters} (uint64 x28 per bin; s_memrealtime ticks; rounds bit 63 = a hot region).
