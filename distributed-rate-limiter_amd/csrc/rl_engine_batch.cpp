@@ -523,14 +523,14 @@ int ensure_staging(rl_engine* e, size_t n) {
 }
 
 // The host-buffer calls' requests into the staging arrays (limiter, op_or_skip: nullable; key
-// null: s_key is filled by the caller, rl_execute_batch_keys).
+// null: s_key is filled by the caller, rl_execute_batch_keys; permits null: rl_quota without them).
 int stage_requests(rl_engine* e, size_t n, const uint64_t* key, const int32_t* permits,
                    const int64_t* now_ns, const uint16_t* limiter, const uint8_t* op_or_skip) {
     const int rc = ensure_staging(e, n);
     if (rc != RL_OK) return rc;
     hipStream_t s = e->stream;
     if (key) HIP_OK(hipMemcpyAsync(e->s_key, key, n * 8, hipMemcpyHostToDevice, s));
-    HIP_OK(hipMemcpyAsync(e->s_permits, permits, n * 4, hipMemcpyHostToDevice, s));
+    if (permits) HIP_OK(hipMemcpyAsync(e->s_permits, permits, n * 4, hipMemcpyHostToDevice, s));
     HIP_OK(hipMemcpyAsync(e->s_now, now_ns, n * 8, hipMemcpyHostToDevice, s));
     if (limiter) HIP_OK(hipMemcpyAsync(e->s_lim, limiter, n * 2, hipMemcpyHostToDevice, s));
     if (op_or_skip) HIP_OK(hipMemcpyAsync(e->s_op, op_or_skip, n, hipMemcpyHostToDevice, s));

@@ -231,6 +231,7 @@ struct rl_engine {
     uint32_t inject_fail = 0;               // rl_tune("fail_batches"): tests of callers' error paths
     uint64_t grows = 0;                     // region-count doublings done (rl_batch_stats)
     DevArray<unsigned long long> retry_dbg; // measurement builds (RL_RETRY_COUNT): k_retry_after's counters
+    DevArray<int64_t> quota_out;            // [2][n] reset / retry of the host form of rl_quota, on first use
     DevArray<uint8_t> topk;                 // rl_top_keys scratch (topk_scratch_bytes), on first use
     DevArray<unsigned long long> tally;     // [kTallyRows][kTallyWords] the host form of rl_tally_batch, on first use
     DevArray<uint8_t> usage;                // rl_limiter_usage / rl_top_consumers scratch, on first use

@@ -1,4 +1,4 @@
-// rl_engine_query.cpp — the read-only queries of an engine: retry-after, heavy-hitter keys, the
+// rl_engine_query.cpp — the read-only queries of an engine: retry-after, quota, heavy-hitter keys, the
 // batch report, the census of a limiter's table, string keys, the table digest and the table check.
 #include "rl_engine_impl.hpp"
 #include "rl_check.hpp"
@@ -72,6 +72,76 @@ extern "C" int rl_retry_after(rl_engine* e, size_t n, const uint64_t* key_hash, 
     HIP_OK(hipStreamSynchronize(s));
     for (size_t i = 0; i < n; ++i)
         if (wait_ms[i] == RL_RETRY_INVALID) return RL_E_INVALID_REQUEST;
+    return RL_OK;
+}
+
+// ---------------------------------------------------------------- quota queries
+// One launch of k_quota, ordered and isolated as run_retry_device's launch is.
+static_assert(RL_QUOTA_INVALID == kQuotaInvalid, "quota: invalid marker");
+static int run_quota_device(rl_engine* e, size_t n, const uint64_t* key, const int64_t* now_ns,
+                            const uint16_t* limiter, const int32_t* permits, const uint8_t* skip,
+                            int64_t* remaining, int64_t* reset_ms, int64_t* retry_ms) {
+    QuotaArgs qa{};
+    qa.key = key; qa.now_ns = now_ns; qa.limiter = limiter; qa.permits = permits; qa.skip = skip;
+    qa.remaining = remaining; qa.reset_ms = reset_ms; qa.retry_ms = retry_ms;
+    qa.lims = e->d_lims; qa.n = (uint32_t)n; qa.n_lim = (uint32_t)e->lims.size();
+    qa.shard_bits = e->shard_bits;
+    HIP_OK(launch_quota(qa, e->stream));
+    return RL_OK;
+}
+
+// permits and retry_ms come together, and skip only with them
+static bool quota_args_ok(const uint64_t* key_hash, const int64_t* now_ns, const int32_t* permits,
+                          const uint8_t* skip, const int64_t* remaining, const int64_t* reset_ms,
+                          const int64_t* retry_ms) {
+    if (!key_hash || !now_ns || !remaining || !reset_ms) return false;
+    return (permits != nullptr) == (retry_ms != nullptr) && (!skip || permits);
+}
+
+extern "C" int rl_quota_device(rl_engine* e, size_t n, const uint64_t* key_hash, const int64_t* now_ns,
+                               const uint16_t* limiter, const int32_t* permits, const uint8_t* skip,
+                               int64_t* remaining, int64_t* reset_ms, int64_t* retry_ms, void* stream) {
+    if (!e) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (n > e->opts.max_batch) return RL_E_TOO_LARGE;
+    if (n == 0) return RL_OK;
+    if (!quota_args_ok(key_hash, now_ns, permits, skip, remaining, reset_ms, retry_ms)) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    StreamJoin join(e->stream, (hipStream_t)stream);
+    HIP_OK(join.err);
+    const int rc = run_quota_device(e, n, key_hash, now_ns, limiter, permits, skip, remaining, reset_ms, retry_ms);
+    HIP_OK(join.finish());
+    return rc;
+}
+
+extern "C" int rl_quota(rl_engine* e, size_t n, const uint64_t* key_hash, const int64_t* now_ns,
+                        const uint16_t* limiter, const int32_t* permits, const uint8_t* skip,
+                        int64_t* remaining, int64_t* reset_ms, int64_t* retry_ms) {
+    if (!e) return RL_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (n > e->opts.max_batch) return RL_E_TOO_LARGE;
+    if (n == 0) return RL_OK;
+    if (!quota_args_ok(key_hash, now_ns, permits, skip, remaining, reset_ms, retry_ms)) return RL_E_INVALID_ARG;
+    (void)hipSetDevice(e->device);
+    // the last batch's status first, as rl_retry_after does (it applies a pending table growth)
+    const int st = collect_status(e);
+    if (st == RL_E_DEVICE) return st;
+    int rc = stage_requests(e, n, key_hash, permits, now_ns, limiter, skip);
+    if (rc == RL_OK) rc = e->quota_out.reserve(2 * n);               // [reset | retry]
+    if (rc != RL_OK) return rc;
+    hipStream_t s = e->stream;
+    int64_t* const d_reset = e->quota_out;
+    int64_t* const d_retry = e->quota_out + n;
+    rc = run_quota_device(e, n, e->s_key, e->s_now, limiter ? e->s_lim : nullptr,
+                          permits ? e->s_permits : nullptr, skip ? e->s_op : nullptr, e->s_remaining,
+                          d_reset, retry_ms ? d_retry : nullptr);
+    if (rc != RL_OK) { (void)hipStreamSynchronize(s); return rc; }
+    HIP_OK(hipMemcpyAsync(remaining, e->s_remaining, n * 8, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(reset_ms, d_reset, n * 8, hipMemcpyDeviceToHost, s));
+    if (retry_ms) HIP_OK(hipMemcpyAsync(retry_ms, d_retry, n * 8, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    for (size_t i = 0; i < n; ++i)
+        if (reset_ms[i] == RL_QUOTA_INVALID) return RL_E_INVALID_REQUEST;
     return RL_OK;
 }
 

@@ -551,6 +551,24 @@ struct RetryArgs {
                                    // buckets probed}
 };
 hipError_t launch_retry_after(const RetryArgs& a, hipStream_t s);
+// Quota queries (rl_quota.hip): the same gather, three answers per query from one lookup: what
+// a peek at now reads, the wait until it reads maxPermits, and (with permits) the retry-after
+// wait. kQuotaInvalid in every output of an invalid query.
+constexpr int64_t kQuotaInvalid = -2;
+struct QuotaArgs {
+    const uint64_t* key;
+    const int64_t* now_ns;
+    const uint16_t* limiter;       // nullable: limiter 0
+    const int32_t* permits;        // nullable: no retry search (retry_ms is null too)
+    const uint8_t* skip;           // nullable; skip[i] != 0: retry 0 without a search
+    int64_t* remaining;
+    int64_t* reset_ms;
+    int64_t* retry_ms;             // nullable with permits
+    const DevLimiter* lims;
+    uint32_t n, n_lim;
+    int shard_bits;
+};
+hipError_t launch_quota(const QuotaArgs& a, hipStream_t s);
 // Heavy-hitter keys of a key stream (rl_topk.hip): a two-row count sketch, an exact
 // {key, count} table of the keys the sketch lets through, a dense list of those that qualify,
 // and the sorted answer. One scratch of fixed size (topk_scratch_bytes) holds all of it.

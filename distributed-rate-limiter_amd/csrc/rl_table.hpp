@@ -1,5 +1,5 @@
 // rl_table.hpp — how a key is found in a limiter's state table, and what a slot found there
-// means, for the kernels off the decision path: retry-after (rl_retry.hip), key migration
+// means, for the kernels off the decision path: retry-after and quota (rl_retry.hpp), key migration
 // (rl_migrate.hip), the census (rl_usage.hip), export / import / growth / sweep
 // (rl_state.hip), snapshot / ordered put (rl_snapshot.hip) and the table shrink
 // (rl_shrink.hip). The decision path has its own region load (rl_region.hpp, rl_hot.hpp).

@@ -106,6 +106,13 @@ int GpuEngine::retryAfter(size_t n, const uint64_t* key, const int32_t* permits,
     return rl_retry_after(e_, n, key, permits, now, limiter, skip, waitMs);
 }
 
+int GpuEngine::quota(size_t n, const uint64_t* key, const int64_t* now, const uint16_t* limiter,
+                     const int32_t* permits, const uint8_t* skip, int64_t* remaining, int64_t* resetMs,
+                     int64_t* retryMs) {
+    std::lock_guard<std::mutex> lk(mu_);
+    return rl_quota(e_, n, key, now, limiter, permits, skip, remaining, resetMs, retryMs);
+}
+
 std::vector<std::pair<uint64_t, uint64_t>> GpuEngine::topKeys(const uint64_t* hashes, size_t n, uint32_t k,
                                                               uint64_t minCount) {
     if (k == 0 || k > RL_TOP_KEYS_MAX || minCount == 0 || (n && !hashes))
@@ -498,6 +505,32 @@ int64_t GpuRateLimiter::retryAfterMillis(const std::string& key, int permits) {
     if (st == RL_E_INVALID_REQUEST || wait == RL_RETRY_INVALID)
         throw IllegalArgumentException("retryAfterMillis: invalid request");
     return wait;                                     // RL_RETRY_NEVER = -1: never
+}
+
+RateLimitQuota GpuRateLimiter::quota(const std::string& key, int permits) {
+    requirePositive(permits);
+    const uint64_t k = keyHash(key);
+    const int32_t p = permits;
+    int64_t now = 0;
+    RateLimitQuota q{cfg_.maxPermits, 0, 0, 0};
+    int st;
+    {
+        // ordered and clocked as retryAfterMillis is
+        std::unique_lock<std::mutex> lk(mu_);
+        cv_.wait(lk, [&] { return !flushing_; });
+        flushing_ = true;
+        now = clock_();
+        lk.unlock();
+        st = engine_->quota(1, &k, &now, &id_, &p, nullptr, &q.remaining, &q.resetMillis,
+                            &q.retryAfterMillis);
+        lk.lock();
+        flushing_ = false;
+        cv_.notify_all();
+    }
+    checkStatus(st, "quota");
+    if (st == RL_E_INVALID_REQUEST || q.resetMillis == RL_QUOTA_INVALID)
+        throw IllegalArgumentException("quota: invalid request");
+    return q;                                        // retryAfterMillis RL_RETRY_NEVER = -1: never
 }
 
 // The census calls run like retryAfterMillis: behind every tryAcquire that has returned, holding

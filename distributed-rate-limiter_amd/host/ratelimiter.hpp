@@ -82,6 +82,16 @@ class RateLimiter {
     virtual void reset(const std::string& key) = 0;                    // :43
 };
 
+// The four numbers of a response's rate-limit headers (the reference's API_EXAMPLES.md:205-213):
+// X-RateLimit-Limit, X-RateLimit-Remaining, X-RateLimit-Reset and the 429's Retry-After, the
+// last two as milliseconds from the query's now.
+struct RateLimitQuota {
+    int64_t limit;              // the configured maxPermits
+    int64_t remaining;          // getAvailablePermits
+    int64_t resetMillis;        // until getAvailablePermits reads `limit` again (0: it does now)
+    int64_t retryAfterMillis;   // until tryAcquire(key, permits) would be allowed (-1: never)
+};
+
 // Micrometer counter stand-ins with the reference's meter names
 // (SlidingWindowRateLimiter.java:67-77, TokenBucketRateLimiter.java:87-93).
 struct Counter {
@@ -148,6 +158,12 @@ class GpuEngine {
     // rl_retry_after: ms until an acquire would be allowed (read-only; skip nullable).
     int retryAfter(size_t n, const uint64_t* key, const int32_t* permits, const int64_t* now,
                    const uint16_t* limiter, const uint8_t* skip, int64_t* waitMs);
+    // rl_quota: per query what getAvailablePermits reads at now, the ms until it reads maxPermits
+    // again and, with permits and retryMs (given together; skip only with them), the retryAfter
+    // wait, from one lookup per key (read-only; limiter nullable).
+    int quota(size_t n, const uint64_t* key, const int64_t* now, const uint16_t* limiter,
+              const int32_t* permits, const uint8_t* skip, int64_t* remaining, int64_t* resetMs,
+              int64_t* retryMs);
     // rl_top_keys: the (key hash, count) pairs of the at most k most frequent of the hashes
     // that occur at least minCount times, count descending then hash ascending; exact.
     // Throws StorageException when the sample overflows the engine's candidate store
@@ -273,10 +289,16 @@ class GpuRateLimiter : public RateLimiter {
 
     // Milliseconds, from the clock's now, until tryAcquire(key, permits) would be allowed on the
     // key's state as it stands (0: now; -1: never, permits > maxPermits): what a caller puts
-    // into Retry-After / X-RateLimit-Reset beside a 429 (the reference's
-    // DemoController.rateLimitExceeded). Not part of the reference's RateLimiter interface.
+    // into Retry-After beside a 429 (the reference's DemoController.rateLimitExceeded). It is
+    // not X-RateLimit-Reset: that is about maxPermits and does not count the local cache
+    // (quota().resetMillis). Not part of the reference's RateLimiter interface.
     // Read-only; it sees every tryAcquire of this object that has returned.
     int64_t retryAfterMillis(const std::string& key, int permits = 1);
+    // Every rate-limit header of one response from one lookup at the clock's now: limit (the
+    // config's maxPermits), remaining (= getAvailablePermits), resetMillis and retryAfterMillis
+    // (= retryAfterMillis(key, permits)). Throws IllegalArgumentException for permits <= 0.
+    // Read-only; it sees every tryAcquire of this object that has returned.
+    RateLimitQuota quota(const std::string& key, int permits = 1);
     // What is in this limiter's table at the clock's now (DBSIZE / INFO keyspace of the
     // reference's Redis; the numbers behind /api/health): slots, live and throttled keys, permits
     // in use. Read-only; sees every tryAcquire of this object that has returned.

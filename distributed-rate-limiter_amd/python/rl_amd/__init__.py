@@ -32,6 +32,7 @@ OP_ACQUIRE, OP_PEEK, OP_RESET = 0, 1, 2
 REM_UNKNOWN, REM_INVALID, REM_ERROR = -1, -2, -3
 RETRY_NEVER, RETRY_INVALID = -1, -2   # RL_RETRY_* (rl_retry_after)
 RETRY_ERROR = -3                      # RL_RETRY_ERROR (rl_router_retry_after: the owner's call failed)
+QUOTA_INVALID = -2                    # RL_QUOTA_INVALID (rl_quota: every output of an invalid query)
 TOP_KEYS_MAX, TOP_KEYS_CANDIDATES = 4096, 65536   # RL_TOP_KEYS_* (rl_top_keys)
 TALLY_ROWS, TALLY_UNKNOWN, TALLY_ACCUMULATE = 256, 255, 1   # RL_TALLY_* (rl_tally_batch)
 USAGE_BINS, USAGE_CANDIDATES = 16, 65536   # RL_USAGE_* (rl_limiter_usage, rl_top_consumers)
@@ -71,7 +72,7 @@ EXPORTS = [
     "rl_owner_of_engine", "rl_router_create", "rl_router_step", "rl_router_finish",
     "rl_router_plan_directory", "rl_router_destroy", "rl_pin_host", "rl_unpin_host",
     "rl_grow_limiter", "rl_limiter_slots", "rl_router_create_ex", "rl_router_stats_get",
-    "rl_retry_after", "rl_retry_after_device",
+    "rl_retry_after", "rl_retry_after_device", "rl_quota", "rl_quota_device",
     "rl_top_keys", "rl_top_keys_device", "rl_router_plan_directory_sampled",
     "rl_limiter_usage", "rl_top_consumers",
     "rl_limiter_digest", "rl_limiter_digest_device",
@@ -284,6 +285,8 @@ def lib():
     L.rl_unpin_host.argtypes = [vp, vp]
     L.rl_retry_after.argtypes = [vp, sz] + [vp] * 6
     L.rl_retry_after_device.argtypes = [vp, sz] + [vp] * 7
+    L.rl_quota.argtypes = [vp, sz] + [vp] * 8
+    L.rl_quota_device.argtypes = [vp, sz] + [vp] * 9
     L.rl_top_keys.argtypes = [vp, sz, vp, u32, ctypes.c_uint64, vp, vp, ctypes.POINTER(sz),
                               ctypes.POINTER(ctypes.c_uint64)]
     L.rl_top_keys_device.argtypes = [vp, sz, vp, u32, ctypes.c_uint64, vp, vp, vp, vp]
@@ -660,6 +663,39 @@ class Engine:
                                            _p(limiter), _p(skip), _p(wait), _p(stream))
         if st != RL_OK:
             raise RlError(st, "rl_retry_after_device")
+
+    def quota(self, limiter, keys, now_ns, permits=None, skip=None):
+        """The rate-limit header numbers of keys[i] at now_ns[i] from one lookup per key (rl_quota):
+        remaining = what available() reads, reset_ms = milliseconds until it reads maxPermits
+        again (0: now), and with `permits` retry_ms = what retry_after() answers (skip[i] != 0: 0
+        without a search). QUOTA_INVALID in every output of an invalid query. `limiter` is one id
+        or an array; permits and now_ns broadcast. Read-only.
+        Returns (remaining, reset_ms, retry_ms | None, status)."""
+        keys = np.ascontiguousarray(keys, np.uint64)
+        n = keys.shape[0]
+        now_ns = np.ascontiguousarray(np.broadcast_to(np.asarray(now_ns, np.int64), (n,)))
+        limiter = np.ascontiguousarray(np.broadcast_to(np.asarray(limiter, np.uint16), (n,)))
+        if permits is not None:
+            permits = np.ascontiguousarray(np.broadcast_to(np.asarray(permits, np.int32), (n,)))
+        skip = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+        remaining = np.zeros(n, np.int64)
+        reset = np.zeros(n, np.int64)
+        retry = None if permits is None else np.zeros(n, np.int64)
+        st = self._L.rl_quota(self._h, n, _p(keys), _p(now_ns), _p(limiter), _p(permits), _p(skip),
+                              _p(remaining), _p(reset), _p(retry))
+        if st not in (RL_OK, RL_E_INVALID_REQUEST):
+            raise RlError(st, "rl_quota")
+        return remaining, reset, retry, st
+
+    def quota_device(self, n, keys, now_ns, limiter, permits, skip, remaining, reset, retry,
+                     stream=None):
+        """rl_quota_device on device buffers (torch tensors or raw pointers; limiter, skip, and
+        permits together with retry may be None); asynchronous, ordered behind the batches
+        submitted before it."""
+        st = self._L.rl_quota_device(self._h, n, _p(keys), _p(now_ns), _p(limiter), _p(permits),
+                                     _p(skip), _p(remaining), _p(reset), _p(retry), _p(stream))
+        if st != RL_OK:
+            raise RlError(st, "rl_quota_device")
 
     def top_keys(self, keys, k, min_count):
         """The keys of a host array that occur at least min_count times, the k most frequent

@@ -253,6 +253,44 @@ int  rl_retry_after_device(rl_engine* e, size_t n, const uint64_t* key_hash,
                            const uint16_t* limiter, const uint8_t* skip,
                            int64_t* wait_ms, void* stream);
 
+/* ---- quota: remaining, exact reset and retry-after in one lookup ---------------------
+ * The numbers of X-RateLimit-Remaining, X-RateLimit-Reset and Retry-After for a batch of
+ * responses, across limiters, from one table lookup per key (X-RateLimit-Limit is the
+ * limiter's configured maxPermits). For query i = (limiter, key_hash, now_ns) with
+ * now = floorDiv(now_ns, 1e6), S the key's state when the call runs (after every batch
+ * submitted before it) and A(t) what RL_OP_PEEK / rl_available reads at millisecond t on S:
+ *   remaining[i] = A(now)                                    (bit-equal to rl_available)
+ *   reset_ms[i]  = min{ t >= now : A(t) == maxPermits } - now
+ *                  the wait until the key's full quota is back; 0 for an absent or expired key.
+ *                  It always exists: reset_ms <= 2 * window_ms + 1 for a now not before the
+ *                  key's newest write. The local cache does not count, as in
+ *                  getAvailablePermits. Exact: the engine's own decision code evaluates A, and
+ *                  a returned t is one it confirmed at t and refuted at t - 1.
+ *   retry_ms[i]  = what rl_retry_after answers for (limiter, key_hash, permits[i], now_ns[i])
+ *                  (the cache counts, RL_RETRY_NEVER for permits > maxPermits); only when
+ *                  `permits` and `retry_ms` are both given. skip[i] != 0 gives retry_ms[i] = 0
+ *                  without a search; remaining and reset_ms are still answered, and a skipped
+ *                  query's permits is not looked at.
+ * reset_ms is not retry_ms of permits = maxPermits when the limiter has a local cache: a
+ * rejecting cache entry delays an acquire, not the quota. A sliding-window query whose now lies
+ * before the key's newest INCR (time regression) with A(now) < maxPermits is searched from that
+ * INCR's time, as in rl_retry_after.
+ * `permits` without `retry_ms`, `retry_ms` without `permits` and `skip` without `permits` are
+ * RL_E_INVALID_ARG. An unknown limiter, or a non-skipped query with permits[i] <= 0, writes
+ * RL_QUOTA_INVALID to every output of that query; the host-buffer call then returns
+ * RL_E_INVALID_REQUEST with the other queries answered. n and the other arguments are checked
+ * as in rl_retry_after. The call changes nothing: no state, no cache entry, no batch statistic,
+ * not the status rl_last_status reports. Multi-GPU: ask the key's owner. */
+#define RL_QUOTA_INVALID (-2)
+int  rl_quota(rl_engine* e, size_t n, const uint64_t* key_hash, const int64_t* now_ns,
+              const uint16_t* limiter, const int32_t* permits, const uint8_t* skip,
+              int64_t* remaining, int64_t* reset_ms, int64_t* retry_ms);
+/* The same on DEVICE buffers, enqueued on `stream` (NULL = the engine's stream) behind every
+ * batch submitted before it; returns launch / argument status only. */
+int  rl_quota_device(rl_engine* e, size_t n, const uint64_t* key_hash, const int64_t* now_ns,
+                     const uint16_t* limiter, const int32_t* permits, const uint8_t* skip,
+                     int64_t* remaining, int64_t* reset_ms, int64_t* retry_ms, void* stream);
+
 /* ---- heavy-hitter keys of a key stream ------------------------------------------
  * The candidates rl_router_plan_directory asks for, computed on the device: with
  * c(h) = #{ i < n : key_hash[i] == h } and H = { h : c(h) >= min_count }, ordered by c

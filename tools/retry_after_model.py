@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""CPU model of the retry-after search (csrc/rl_retry.hip `retry_search`) for ONE query: the
+"""CPU model of the retry-after search (csrc/rl_retry.hpp `retry_search`) for ONE query: the
 exact predicate P(t) restated from csrc/rl_device.hpp (tb_step / sw_step_g / sw_step_cache: would
 an acquire of p at millisecond t be allowed on this state, not applied), and around it the
 kernel's search step for step: t0, the closed-form guess, its check at guess - 2 .. guess + 2
@@ -132,8 +132,18 @@ def tb_refill(L, t, s):
     return x if x < L.capacity else L.capacity
 
 
-def pred(L, p, t, s):
-    """P(t): an acquire of p at t is allowed on state s, not applied."""
+def peek(L, t, s):
+    """What getAvailablePermits reads at t on state s (RL_OP_PEEK's remaining): no cache."""
+    if L.algo == TB:
+        return d2l(tb_refill(L, t, s))
+    return max(0, L.max - sw_est(L, t, s))
+
+
+def pred(L, p, t, s, full=False):
+    """P(t): an acquire of p at t is allowed on state s, not applied. `full`: the whole quota is
+    available at t (the peek reads max; p and the cache word are not looked at)."""
+    if full:
+        return peek(L, t, s) == L.max
     if L.algo == TB:
         if p > L.max:
             return False
@@ -157,8 +167,11 @@ def sw_guess_window(W, lo, prev, curr, room, w):
     return t if t < W + w else -1
 
 
-def search(L, p, now, s, stats=None):
-    """The kernel's per-query answer for a key that has a slot (after the permits checks)."""
+def search(L, p, now, s, stats=None, full=False):
+    """The kernel's per-query answer for a key that has a slot (after the permits checks).
+    `full`: the wait for the whole quota (rl_quota's reset: p = max, the cache word ignored)."""
+    if full:
+        p = L.max
     if p <= 0:
         return INVALID
     if p > L.max:
@@ -172,12 +185,12 @@ def search(L, p, now, s, stats=None):
             t0 = max(t0, s["b1_start"] + s["b1_off"])
         elif s["b0_cnt"]:
             t0 = max(t0, s["b1_start"] - w + s["b0_off"])
-        if L.cache_ttl > 0:
+        if L.cache_ttl > 0 and not full:
             t0 = max(t0, s["x"])
         hi = s["b1_start"] + 2 * w
     if stats is not None:
         stats["queries"] = stats.get("queries", 0) + 1
-    if pred(L, p, t0, s):
+    if pred(L, p, t0, s, full):
         return t0 - now
     if stats is not None:
         stats["searches"] = stats.get("searches", 0) + 1
@@ -224,10 +237,10 @@ def search(L, p, now, s, stats=None):
     # ---- the guess and two neighbours either way, by the exact predicate
     lo_f, hi_t, hi_known = t0, hi, False
     t = g
-    if pred(L, p, t, s):
+    if pred(L, p, t, s, full):
         k = 0
         while True:
-            if t - 1 == t0 or not pred(L, p, t - 1, s):
+            if t - 1 == t0 or not pred(L, p, t - 1, s, full):
                 return t - now
             t -= 1
             if k == 2:
@@ -239,18 +252,18 @@ def search(L, p, now, s, stats=None):
         k = 0
         while k < 2 and t < hi:
             t += 1
-            if pred(L, p, t, s):
+            if pred(L, p, t, s, full):
                 return t - now
             lo_f = t
             k += 1
     # ---- bisection on (lo_f: false, hi_t: true)
     if stats is not None:
         stats["bisections"] = stats.get("bisections", 0) + 1
-    if not hi_known and not pred(L, p, hi_t, s):
+    if not hi_known and not pred(L, p, hi_t, s, full):
         return NEVER
     while hi_t - lo_f > 1:
         mid = lo_f + (hi_t - lo_f) // 2
-        if pred(L, p, mid, s):
+        if pred(L, p, mid, s, full):
             hi_t = mid
         else:
             lo_f = mid
